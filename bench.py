@@ -3,7 +3,15 @@
 batch 256 per GPU, 1x MI355X), on synthetic 224x224 images and C = 10 class prompts.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--classes C]
-                  [--method adapter|lora] [--no-cpu-baseline]
+                  [--method adapter|lora] [--dump-outputs DIR] [--full [--no-cpu-baseline]]
+
+A plain run sets up, warms up, times the K steps and prints the result line (`value`,
+`ms_per_step`, the image tower's share of the timed loop). `--full` adds what takes runs of its
+own: the per-launch GEMM timing of one extra step (`roofline`, `library_gemm`), the train
+transform's launch time (`train_transform`) and the oracle on the host (`cpu_baseline`).
+`--dump-outputs DIR` writes what the last timed step returned (`loss`, `probs`) as
+DIR/<name>.npy in float32; the weights and the batch are seeded, so two builds run with the same
+arguments see identical inputs.
 
 For N > 1 bench.py starts the N ranks itself (torch.distributed.run in a child process, one
 process per GPU, RCCL over xGMI; launching it under torch.distributed.run works too); per-GPU work is fixed
@@ -241,6 +249,22 @@ def time_train_transform(B, dev, reps=20):
             "achieved_GBps": round(nbytes / (us * 1e-6) / 1e9, 1), "peak_GBps": PEAK_HBM / 1e9}
 
 
+def dump_outputs(out_dir, outputs, rank=0, limit=64 << 20):
+    """What trainer.step returned in the last timed step, as <out_dir>/<name>.npy in float32
+    (rank r > 0 of a multi-GPU job writes <name>.rank<r>.npy: its own shard's outputs). The
+    step's outputs are the scalar loss and the B x C probabilities: far below the 64 MB that a
+    dump may take, so nothing is sampled."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    total = 0
+    for name, t in outputs.items():
+        a = t.detach().to(torch.float32).cpu().numpy()
+        total += a.nbytes
+        if total > limit:
+            raise SystemExit(f"--dump-outputs: {name} takes the dump past {limit} bytes")
+        np.save(os.path.join(out_dir, name + (f".rank{rank}" if rank else "") + ".npy"), a)
+
+
 def host_cores():
     """(cores to use, os.cpu_count(), cgroup CPU quota in cores or None). SURVEY §8(d) asks for
     os.cpu_count() threads; on a shared GPU box the process's cgroup may grant fewer CPUs than
@@ -353,7 +377,14 @@ def main():
     ap.add_argument("--batch", type=int, default=256)
     ap.add_argument("--classes", type=int, default=10)
     ap.add_argument("--method", default="adapter", choices=["adapter", "lora", "vanilla"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: the per-launch GEMM timing of "
+                         "one extra step (roofline, library_gemm), the train transform and the "
+                         "CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full: leave the CPU baseline out")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (loss, probs) as DIR/<name>.npy")
     ap.add_argument("--force-dist", action="store_true",
                     help="initialise the RCCL process group and the DP exchange even at N=1 "
                          "(exercises the collective path; launch through torch.distributed.run)")
@@ -380,6 +411,8 @@ def main():
     ap.add_argument("--resid32", action="store_true",
                     help="A/B knob: the image tower's residual stream in f32 instead of IEEE half")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -449,27 +482,27 @@ def main():
     dt = t.item()
     ms = dt / args.steps * 1e3
     total_ips = world * B * args.steps / dt
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"loss": loss, "probs": probs}, rank)
 
-    # dominant kernel (lc_gemm_nt family) timed live with HIP events on its launch stream,
-    # over one extra, untimed step
-    with GemmTimer(ops) as gt:
-        trainer.eager_step(x, y, tok)
-    gs = gt.summary()
     img_ms = tt.ms()
     img_src = "timed loop"
-    if img_ms is None:  # graph replay: the tower's methods are not called per step
-        with TowerTimer(trainer.img) as tt2:
+    if args.full:
+        # dominant kernel (lc_gemm_nt family) timed live with HIP events on its launch stream,
+        # over one extra, untimed step
+        with GemmTimer(ops) as gt:
             trainer.eager_step(x, y, tok)
-            trainer.eager_step(x, y, tok)
-        img_ms, img_src = tt2.ms(), "eager steps after the timed loop (graph mode)"
-    tf_stats = time_train_transform(B, dev)
+        gs = gt.summary()
+        if img_ms is None:  # graph replay: the tower's methods are not called per step
+            with TowerTimer(trainer.img) as tt2:
+                trainer.eager_step(x, y, tok)
+                trainer.eager_step(x, y, tok)
+            img_ms, img_src = tt2.ms(), "eager steps after the timed loop (graph mode)"
+        tf_stats = time_train_transform(B, dev)
 
     if rank == 0:
         f_img = F_IMG[args.method]
         f_step = B * f_img + C * F_TXT[args.method] + 6 * B * C * 512
-        achieved = gs["pp_flops"] / (gs["pp_ms"] * 1e-3)
-        traffic, traffic_src = pmc_traffic()
-        n_pp = max(gs["pp_n"], 1)
         out = {
             "metric": "images/sec/GPU (ViT-B/16 fwd+bwd, bs=256) + online A_AUC on CIFAR-100",
             "metric_note": "value is the throughput half only; A_AUC needs CIFAR-100 and CLIP "
@@ -505,7 +538,9 @@ def main():
                        "launch": "hip_graph" if graph else "eager"},
             "images_per_s_per_gpu": round(total_ips / world, 2),
             "mfma_frac_step": round(f_step / (ms * 1e-3) / PEAK_BF16, 4),
-            "image_tower": {"ms_fwd_bwd": round(img_ms, 3),
+            # (a graph replay calls no tower method per step: its spans come with --full)
+            "image_tower": None if img_ms is None else {
+                            "ms_fwd_bwd": round(img_ms, 3),
                             "tflops": round(B * f_img / (img_ms * 1e-3) / 1e12, 1),
                             "mfma_frac": round(B * f_img / (img_ms * 1e-3) / PEAK_BF16, 4),
                             "mfma_frac_step_bound": round(B * f_img / (ms * 1e-3) / PEAK_BF16, 4),
@@ -516,35 +551,41 @@ def main():
                                     "spans around the tower's fwd and bwd on the main stream; "
                                     "mfma_frac_step_bound = the same with the whole step time "
                                     "(a lower bound of mfma_frac)"},
-            "roofline": {"bound": "mfma",
-                         "kernel": "gemm8_kernel<EPI 0|2|6|7, bf16> (256x256 phase-interleaved "
-                                   "bf16 MFMA GEMM: QKV, out-proj, c_fc+QuickGELU+QuickGELU', "
-                                   "c_proj fwd; out-proj, c_fc, c_proj dX)",
-                         "achieved": round(achieved / 1e12, 2), "peak": PEAK_BF16 / 1e12,
-                         "unit": "TFLOP/s", "frac": round(achieved / PEAK_BF16, 4),
-                         "traffic": None if traffic is None else round(traffic),
-                         "traffic_unit": "bytes per launch (PMC FETCH_SIZE*2 + WRITE_SIZE)",
-                         "traffic_source": traffic_src,
-                         "algorithmic_bytes_per_launch": round(gs["pp_bytes"] / n_pp),
-                         "flops_per_launch": round(gs["pp_flops"] / n_pp),
-                         "launches_per_step": gs["pp_n"],
-                         "avg_launch_ms": round(gs["pp_ms"] / n_pp, 4),
-                         "main_stream_gemm_share_of_step": round(gs["ms"] / ms, 3),
-                         "side_stream_gemm_ms": round(gs["side_ms"], 3),
-                         "note": "launches of the dominant kernel on the main (image-chain) "
-                                 "stream, timed with HIP events around each launch of one extra "
-                                 "eager step"},
-            # the one plain GEMM the library routes to hipBLASLt (QKV dX at 256 images), apart
-            "library_gemm": {"kernel": "hipBLASLt (QKV input gradient, plain bf16 GEMM)",
-                             "launches_per_step": gs["lib_n"],
-                             "avg_launch_ms": round(gs["lib_ms"] / max(gs["lib_n"], 1), 4),
-                             "tflops": round(gs["lib_flops"] / max(gs["lib_ms"], 1e-9) / 1e9, 1)},
             "runtime": {"GPU_MAX_HW_QUEUES": HW_QUEUES,
                         "side_streams": 1 if trainer._merge_side_streams() else 2,
                         "side_stream_cus": trainer.side_cus},
-            "train_transform": tf_stats,
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full:
+            achieved = gs["pp_flops"] / (gs["pp_ms"] * 1e-3)
+            traffic, traffic_src = pmc_traffic()
+            n_pp = max(gs["pp_n"], 1)
+            out.update({
+                "roofline": {"bound": "mfma",
+                             "kernel": "gemm8_kernel<EPI 0|2|6|7, bf16> (256x256 phase-interleaved "
+                                       "bf16 MFMA GEMM: QKV, out-proj, c_fc+QuickGELU+QuickGELU', "
+                                       "c_proj fwd; out-proj, c_fc, c_proj dX)",
+                             "achieved": round(achieved / 1e12, 2), "peak": PEAK_BF16 / 1e12,
+                             "unit": "TFLOP/s", "frac": round(achieved / PEAK_BF16, 4),
+                             "traffic": None if traffic is None else round(traffic),
+                             "traffic_unit": "bytes per launch (PMC FETCH_SIZE*2 + WRITE_SIZE)",
+                             "traffic_source": traffic_src,
+                             "algorithmic_bytes_per_launch": round(gs["pp_bytes"] / n_pp),
+                             "flops_per_launch": round(gs["pp_flops"] / n_pp),
+                             "launches_per_step": gs["pp_n"],
+                             "avg_launch_ms": round(gs["pp_ms"] / n_pp, 4),
+                             "main_stream_gemm_share_of_step": round(gs["ms"] / ms, 3),
+                             "side_stream_gemm_ms": round(gs["side_ms"], 3),
+                             "note": "launches of the dominant kernel on the main (image-chain) "
+                                     "stream, timed with HIP events around each launch of one "
+                                     "extra eager step"},
+                # the one plain GEMM the library routes to hipBLASLt (QKV dX at 256 images), apart
+                "library_gemm": {"kernel": "hipBLASLt (QKV input gradient, plain bf16 GEMM)",
+                                 "launches_per_step": gs["lib_n"],
+                                 "avg_launch_ms": round(gs["lib_ms"] / max(gs["lib_n"], 1), 4),
+                                 "tflops": round(gs["lib_flops"] / max(gs["lib_ms"], 1e-9) / 1e9, 1)},
+                "train_transform": tf_stats,
+            })
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline()
         print(json.dumps(out), flush=True)
     if dp:

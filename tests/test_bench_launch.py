@@ -52,6 +52,37 @@ def test_main_spawns_only_without_launcher(monkeypatch):
     assert calls == [(1, ["--force-dist"])]
 
 
+def test_dump_outputs_writes_float32_arrays(tmp_path):
+    # --dump-outputs DIR: one float32 <name>.npy per output of the step; other ranks add .rank<r>
+    import numpy as np
+    import torch
+    outs = {"loss": torch.tensor([1.5], dtype=torch.float64),
+            "probs": torch.full((4, 3), 0.25, dtype=torch.bfloat16)}
+    d = tmp_path / "dump"
+    bench.dump_outputs(str(d), outs)
+    bench.dump_outputs(str(d), outs, rank=1)
+    assert sorted(os.listdir(d)) == ["loss.npy", "loss.rank1.npy", "probs.npy", "probs.rank1.npy"]
+    loss, probs = np.load(d / "loss.npy"), np.load(d / "probs.npy")
+    assert loss.dtype == probs.dtype == np.float32
+    assert loss.tolist() == [1.5] and probs.shape == (4, 3) and (probs == 0.25).all()
+
+
+def test_dump_outputs_refuses_more_than_the_limit(tmp_path):
+    import torch
+    outs = {"loss": torch.zeros(1), "probs": torch.zeros(4, 3)}  # 4 + 48 bytes as float32
+    bench.dump_outputs(str(tmp_path / "fits"), outs, limit=52)
+    with pytest.raises(SystemExit, match="probs takes the dump past 51 bytes"):
+        bench.dump_outputs(str(tmp_path / "over"), outs, limit=51)
+    assert os.listdir(tmp_path / "over") == ["loss.npy"]  # nothing past the limit is written
+
+
+def test_steps_must_be_positive(monkeypatch):
+    monkeypatch.setenv("WORLD_SIZE", "1")
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "0"])
+    with pytest.raises(SystemExit, match="--steps must be >= 1"):
+        bench.main()
+
+
 def test_rank_checks_world_against_gpus(monkeypatch):
     # a rank whose launcher started a different number of processes than --gpus asks for
     monkeypatch.setenv("WORLD_SIZE", "2")

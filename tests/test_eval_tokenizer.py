@@ -2,8 +2,8 @@
 10-bucket table, the confusion matrix, the summary metrics) against direct restatements of
 methods/_trainer.py:367-378, 519-534 and sklearn; the BPE tokenizer's structural pins (vocab
 layout, special ids, ids of the byte symbols derived from the byte table, round trip). The
-tokenizer tests need the merges file: /root/reference's copy when present (skipped otherwise —
-it is data the build does not ship)."""
+tokenizer tests read the merges from tests/golden/clip_bpe_merges.txt.gz: the part of the public
+CLIP merges file that the 49 408-id vocabulary uses (tests/golden/make_bpe_golden.py)."""
 import math
 import os
 
@@ -13,7 +13,7 @@ import torch
 
 from lcclip import evaluate as ev
 
-BPE = "/root/reference/models/clip/bpe_simple_vocab_16e6.txt.gz"
+BPE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "clip_bpe_merges.txt.gz")
 
 
 def interpret_ref(y, pred, n_tasks):
@@ -76,7 +76,6 @@ def test_auc_tracker_periods():
     assert t.results()["test_acc"] == [7 / 30, 13 / 30, 19 / 30, 25 / 30]
 
 
-@pytest.mark.skipif(not os.path.isfile(BPE), reason="BPE merges file not available")
 def test_tokenizer_structure():
     from lcclip.tokenizer import BPETokenizer, byte_table
     t = BPETokenizer(BPE)
@@ -93,7 +92,6 @@ def test_tokenizer_structure():
     assert t.decoder[t.encoder["a</w>"]] == "a</w>"
 
 
-@pytest.mark.skipif(not os.path.isfile(BPE), reason="BPE merges file not available")
 def test_labels_tokenize_with_bpe():
     from lcclip import AdapterCLIP
     from lcclip.tokenizer import BPETokenizer
@@ -146,7 +144,6 @@ def test_labels_tokenize_matches_fixture_rows():
         assert tok[i, :len(ids)].tolist() == ids and (tok[i, len(ids):] == 0).all()
 
 
-@pytest.mark.skipif(not os.path.isfile(BPE), reason="BPE merges file not available")
 def test_tokenizer_reproduces_token_fixture():
     from lcclip.tokenizer import BPETokenizer
     t = BPETokenizer(BPE)
@@ -172,7 +169,6 @@ def test_token_fixture_matches_independent_tokenizer():
         assert hf[d["template"].format(name)] == ids, name
 
 
-@pytest.mark.skipif(not os.path.isfile(BPE), reason="BPE merges file not available")
 def test_tokenizer_matches_independent_tokenizer_free_text():
     """Free text (punctuation, digits, case, underscores, contractions) through lcclip's BPE vs the
     independent implementation's committed ids."""

@@ -6,7 +6,7 @@
 #   tests            the whole `-m gpu` suite (the driver's command)
 #   tests:<args>     pytest with <args> (e.g. tests:tests/test_f16_gpu.py)
 #   smoke            __graft_entry__.smoke()
-#   bench            the default bench line (the driver's command)
+#   bench            the default bench line with every figure (bench.py --full)
 #   lines            the other bench lines DESIGN quotes: C = 100, LoRA B = 128, the fp16 image
 #                    tower, MaPLe (bf16 / fp8), MVP
 #   ab:<n>           <n> interleaved pairs of bench runs, the working tree vs the library in
@@ -26,10 +26,10 @@ step() {
            run tests 900 python -u -m pytest tests -m gpu -x -q --timeout 200 --timeout-method thread ;;
     tests:*) run tests_sel 900 $PY ${1#tests:} ;;
     smoke) run smoke 150 python -u -c "import __graft_entry__ as g; g.smoke()" ;;
-    bench) run bench_default 300 python -u bench.py ;;
-    lines) run bench_c100 300 $B --classes 100
-           run bench_lora 300 $B --method lora --batch 128
-           run bench_fp16 300 $B --image-precision fp16
+    bench) run bench_default 300 python -u bench.py --full ;;
+    lines) run bench_c100 300 $B --full --classes 100
+           run bench_lora 300 $B --full --method lora --batch 128
+           run bench_fp16 300 $B --full --image-precision fp16
            run bench_maple 300 python -u tools/bench_maple.py
            run bench_mvp 300 python -u tools/bench_mvp.py ;;
     ab:*) for i in $(seq 1 ${1#ab:}); do

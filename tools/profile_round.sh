@@ -15,8 +15,8 @@ if [ "${TESTS:-0}" = "1" ]; then
   run tests 600 python -u -m pytest tests -m gpu -x -q --timeout 200 --timeout-method thread
   run smoke 150 python -u -c "import __graft_entry__ as g; g.smoke()"
 fi
-run bench 400 python -u bench.py --steps 20 --warmup 5 ${BENCH_ARGS:-}
-run trace 300 rocprofv3 --kernel-trace --stats --output-format csv -d $P/trace -o run -- python bench.py --steps 5 --warmup 2 --no-cpu-baseline
+run bench 400 python -u bench.py --full --steps 20 --warmup 5 ${BENCH_ARGS:-}
+run trace 300 rocprofv3 --kernel-trace --stats --output-format csv -d $P/trace -o run -- python bench.py --full --steps 5 --warmup 2 --no-cpu-baseline
 run fetch 200 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $P/fetch -o p -- python bench.py --steps 1 --warmup 1 --no-cpu-baseline
 run write 200 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $P/write -o p -- python bench.py --steps 1 --warmup 1 --no-cpu-baseline
 python tools/pmc_traffic.py $P/fetch $P/write gpurun_out/${TAG}_gemm_traffic.json > gpurun_out/${TAG}_pmc.log 2>&1
