@@ -235,11 +235,14 @@ def test_layernorm_bwd_fp8_matches_quant(ops, dev, rows, D, xdt):
 
 
 @pytest.mark.parametrize("n_seq,L,H,causal", [(4, 197, 12, False), (2, 199, 12, False),
-                                              (3, 77, 8, True), (2, 40, 2, False)])
+                                              (3, 77, 8, True), (2, 40, 2, False),
+                                              (89, 197, 12, False)])
 def test_attn_bwd_fp8_matches_quant(ops, dev, n_seq, L, H, causal):
     """The attention backward writing dq|dk|dv as the fp8 QKV-dX operand (MaPLe's fp8 mode)
-    equals attn_bwd followed by quant_fp8 bit for bit: persistent (L = 197, 199) and
-    one-item-per-workgroup (L = 77 causal, 40) variants."""
+    equals attn_bwd followed by quant_fp8 bit for bit. The persistent template (L = 197, 199)
+    runs one item per workgroup at 4 and 2 sequences (48 and 24 items) and walks several items
+    per workgroup at 89 (1068 items >= 4 * CUs); L = 77 causal and 40 are the
+    one-item-per-workgroup template."""
     g = torch.Generator(device=dev).manual_seed(n_seq * L + H)
     D = H * 64
     M = n_seq * L
