@@ -571,6 +571,106 @@ int lc_vit_embed_ln_f16(hipStream_t stream, int n_img, int n_patch, int D, const
                         const float* ln_pre_b, float* x0, const float* ln1_w, const float* ln1_b,
                         void* y, float* mean1, float* rstd1);
 
+/* ---------------------------------------------------------------- MVP-CLIP training method
+ * (mvp.hip). f32 in, f32 out, row-major. Pool P <= 64, selection K <= 8 (K <= P), E <= 1024,
+ * C <= 1024, query / key width W <= 4096; other shapes return LC_EINVAL. No floating-point
+ * atomics and fixed-order reductions: two launches on the same inputs are bit-identical. */
+
+/* distance[b][p] = 1 - cos(query[b], key[p]) (each norm clamped at 1e-8, torch's
+ * cosine_similarity), scaled = distance * (count[p] + 1) (count NULL: unscaled); idx [B,K] the K
+ * smallest scaled distances per row in ascending order, ties to the lower index; dist [B,K] the
+ * selected unscaled distances; qnorm [B] / knorm [P] the clamped norms (for the backward);
+ * hist [P] (may be NULL) += the bincount of idx (integer atomics).
+ * Replaces: models/mvp_clip.py:224-235 (cosine distance, topk, the distance gather), :253
+ * (bincount). */
+int lc_mvp_select(hipStream_t stream, int B, int P, int W, int K, const float* query, long ldq,
+                  const float* key, long ldk, const float* count, int64_t* idx, float* dist,
+                  float* qnorm, float* knorm, unsigned long long* hist);
+
+/* The similarity loss of the selection. contrastiv = 0: loss = mean(dist). contrastiv = 1
+ * (K == 1 only: the reference's key_wise_distance[topk] / mass[topk] broadcasts [B,1,P] against
+ * [B,1] to [B,B,P] and raises for K > 1 at a general batch):
+ *   A = mean_{a,b,p} exp((1 - cos(key[t_a], key[p])) / mass[t_b]),
+ *   D = mean_{a,b} exp(dist[b] / mass[t_a]),  loss = -log(A / (D + A) + 1e-6),
+ * t = idx, mass = count + 1. kcos [P,P], rawgd [B K], rawW [P,P], coef [2] are kept for
+ * lc_mvp_simloss_bwd (kcos / rawW unused and may be NULL when contrastiv = 0).
+ * Replaces: models/mvp_clip.py:239-248. */
+int lc_mvp_simloss(hipStream_t stream, int B, int P, int W, int K, int contrastiv,
+                   const float* key, long ldk, const float* count, const int64_t* idx,
+                   const float* dist, const float* knorm, float* kcos, float* rawgd, float* rawW,
+                   float* coef, float* loss);
+
+/* dkey [P,W] = upstream[0] * d loss / d key (upstream a device scalar, NULL = 1): one workgroup
+ * per pool entry walking its (b, s) contributors in ascending order; unselected entries of the
+ * plain form get exact zeros. Backward of lc_mvp_select's distances + lc_mvp_simloss. */
+int lc_mvp_simloss_bwd(hipStream_t stream, int B, int P, int W, int K, int contrastiv,
+                       const float* query, long ldq, const float* key, long ldk,
+                       const int64_t* idx, const float* dist, const float* qnorm,
+                       const float* knorm, const float* kcos, const float* rawgd,
+                       const float* rawW, const float* coef, const float* upstream, float* dkey,
+                       long ldd);
+
+/* mean = 0: out [B K, R] = table[idx]; mean = 1: out [B, R] = mean_s table[idx[b][s]]. An index
+ * outside [0, P) gives a NaN row. Replaces: e_prompts[topk], mask[topk].mean(1)
+ * (models/mvp_clip.py:236-237). */
+int lc_pool_gather(hipStream_t stream, int B, int K, int P, long R, const float* table, long ldt,
+                   const int64_t* idx, float* out, int mean);
+
+/* dtable[p] = alpha * sum_{(b,s): idx[b][s] = p} g[n], n = b K + s (shared_s = 1: g is [B, R]
+ * and every s of image b reads row b, the backward of mean = 1 with alpha = 1/K). Rows are summed
+ * in ascending (b, s) order, each read once with 16-B loads (any R); unselected entries are exact
+ * zeros. ws: P + 1 + B K ints (the counting sort of idx). Replaces: the index_put / one_hot^T @ g
+ * backward of the pool gathers. */
+int lc_pool_gather_bwd(hipStream_t stream, int B, int K, int P, long R, const int64_t* idx,
+                       const float* g, long ldg, int shared_s, float alpha, float* dtable,
+                       long ldd, int* ws, long ws_ints);
+
+/* u = exp(*logit_scale) img_n txt_n^T (the unmasked logits); logits = u * 2 sigmoid(maskrows)
+ * + cmask (maskrows [B, >= C] pre-sigmoid selected mask rows or NULL; cmask [C] 0 / -inf or
+ * NULL); probs = softmax(logits); nll[b] = -log probs[b][y_b]; q1[b] = 1 - probs[b][y_b],
+ * summed as sum_{c != y} e_c / Z (no cancellation at a peaky softmax). A label outside [0, C)
+ * gives a NaN nll, one on a -inf column +inf, and both a NaN q1 (which lc_mvp_head_bwd and the
+ * scores spread over the row), so lc_check_finite skips the update.
+ * Replaces: methods/mvp_clip.py:265-276, the sigmoid * 2 of models/mvp_clip.py:263. */
+int lc_mvp_head_fwd(hipStream_t stream, int B, int C, int E, const float* img_n,
+                    const float* txt_n, const float* logit_scale, const float* maskrows, long ldm,
+                    const float* cmask, const int64_t* labels, float* logits, float* u,
+                    float* probs, float* nll, float* q1);
+
+/* lbar = mean_b nll[b]; w = (1 - alpha) + alpha * gsf_sum[0] * inv_n (gsf_sum NULL: w = 1);
+ * loss = lbar * w. Replaces: F.nll_loss's mean and methods/mvp_clip.py:277-280 (use_gsf). */
+int lc_mvp_loss_mean(hipStream_t stream, int B, const float* nll, const float* gsf_sum,
+                     float alpha, float inv_n, float* loss, float* w, float* lbar);
+
+/* G [C,E] = scale * s * sum_b m[b][c] (probs[b][c] - [y_b == c]) img_n[b] — the batch gradient
+ * of methods/mvp_clip.py:230-236 in closed form (scale = 1 / global batch). An output: data
+ * parallelism sums it over ranks before lc_mvp_score. */
+int lc_mvp_score_g(hipStream_t stream, int B, int C, int E, const float* img_n,
+                   const float* probs, const float* q1, const float* maskrows, long ldm,
+                   const float* logit_scale, const int64_t* labels, float scale, float* G);
+
+/* ign[b] = 1 - cos(sample_grad_b, G[y_b]), sample_grad_b = s m[b][y_b] (-q1[b]) img_n[b];
+ * cps[b] = 1 - cos(txt_n[y_b], img_n[b]) + margin; ign_sum[0] (may be NULL) = sum_b ign[b]^gamma.
+ * Cosines with torch's eps. Replaces: the loop of B backward passes and the two scores of
+ * methods/mvp_clip.py:204-254. */
+int lc_mvp_score(hipStream_t stream, int B, int C, int E, const float* img_n, const float* txt_n,
+                 const float* G, const float* q1, const float* maskrows, long ldm,
+                 const float* logit_scale, const int64_t* labels, float margin, float gamma,
+                 float* ign, float* cps, float* ign_sum);
+
+/* AFS (methods/mvp_clip.py:264-266): the image feature divided by cps, then normalised:
+ * out_n = sign(cps) img_n, out_norms = sign(cps) norms (the divisor lc_head_feat_grad needs for
+ * the gradient to the undivided feature); cps = 0 gives NaN. */
+int lc_mvp_afs(hipStream_t stream, int B, int E, const float* img_n, const float* norms,
+               const float* cps, float* out_n, float* out_norms);
+
+/* dz = w[0] (probs - onehot) * inv_b (w NULL: 1); dlog [B,C] = dz m, the gradient to the
+ * unmasked logits in lc_head_feat_grad's layout; dmask [B, NC] (may be NULL) = dz u m'(maskrows),
+ * columns C .. NC-1 zero. An invalid label (a NaN q1) gives a NaN row. */
+int lc_mvp_head_bwd(hipStream_t stream, int B, int C, int NC, const float* probs, const float* q1,
+                    const float* u, const float* maskrows, long ldm, const int64_t* labels,
+                    const float* w, float inv_b, float* dlog, float* dmask, long ldd);
+
 #ifdef __cplusplus
 }
 #endif

@@ -13,7 +13,8 @@ from ._lib import LcError, load as load_library
 from .adapter_clip import AdapterCLIP, freeze_backbone
 from .clip_loader import available_models, load
 from .model import CLIP, build_model
+from .mvp_trainer import MVPTrainer
 from .trainer import OnlineTrainer, remap_labels
 
-__all__ = ["AdapterCLIP", "CLIP", "OnlineTrainer", "LcError", "available_models", "build_model",
-           "freeze_backbone", "load", "load_library", "remap_labels"]
+__all__ = ["AdapterCLIP", "CLIP", "MVPTrainer", "OnlineTrainer", "LcError", "available_models",
+           "build_model", "freeze_backbone", "load", "load_library", "remap_labels"]

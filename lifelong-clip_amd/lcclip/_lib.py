@@ -78,6 +78,20 @@ SIGNATURES = {
     "lc_head_feat_grad": [P, c_int, c_int, c_int, P, c_long, c_long, P, P, P, P, P, P],
     "lc_grad_pow2_normalize": [P, c_long, P, P, c_int],
     "lc_add_unscaled": [P, c_long, P, P, P],
+    "lc_mvp_select": [P, c_int, c_int, c_int, c_int, P, c_long, P, c_long, P, P, P, P, P, P],
+    "lc_mvp_simloss": [P, c_int, c_int, c_int, c_int, c_int, P, c_long, P, P, P, P, P, P, P, P, P],
+    "lc_mvp_simloss_bwd": [P, c_int, c_int, c_int, c_int, c_int, P, c_long, P, c_long, P, P, P, P,
+                           P, P, P, P, P, P, c_long],
+    "lc_pool_gather": [P, c_int, c_int, c_int, c_long, P, c_long, P, P, c_int],
+    "lc_pool_gather_bwd": [P, c_int, c_int, c_int, c_long, P, P, c_long, c_int, c_float, P, c_long,
+                           P, c_long],
+    "lc_mvp_head_fwd": [P, c_int, c_int, c_int, P, P, P, P, c_long, P, P, P, P, P, P, P],
+    "lc_mvp_loss_mean": [P, c_int, P, P, c_float, c_float, P, P, P],
+    "lc_mvp_score_g": [P, c_int, c_int, c_int, P, P, P, P, c_long, P, P, c_float, P],
+    "lc_mvp_score": [P, c_int, c_int, c_int, P, P, P, P, P, c_long, P, P, c_float, c_float, P, P,
+                     P],
+    "lc_mvp_afs": [P, c_int, c_int, P, P, P, P, P],
+    "lc_mvp_head_bwd": [P, c_int, c_int, c_int, P, P, P, P, c_long, P, P, c_float, P, P, c_long],
     "lc_device_cu_count": [c_int, P],
     "lc_stream_create_cumask": [c_int, c_int, c_int, c_int, P],
     "lc_stream_destroy": [P],

@@ -274,3 +274,167 @@ def maple_image_apply(tower, img, shared, deep, training):
     _check_frozen(tower.stack)
     save = torch.is_grad_enabled() and (shared.requires_grad or any(d.requires_grad for d in deep))
     return _MapleImageFn.apply(tower, img, bool(training), save, shared, *deep)
+
+
+# ------------------------------------------------------------------ MVP-CLIP method (mvp.hip)
+class _MvpSelectFn(torch.autograd.Function):
+    """models/mvp_clip.py:224-248, 253 on lc_mvp_select + lc_mvp_simloss: key distance, top-k
+    (count-scaled under use_contrastiv), the selected distances, the bincount and the similarity
+    loss; backward gives dkey (the query is a no-grad quantity)."""
+
+    @staticmethod
+    def forward(ctx, key, query, count, k, contrastiv, hist):
+        key_d = key.detach()
+        query = query.detach().contiguous().float()
+        B, P, dev = query.shape[0], key_d.shape[0], query.device
+        idx = torch.empty(B, k, dtype=torch.int64, device=dev)
+        dist = torch.empty(B, k, dtype=F32, device=dev)
+        qn = torch.empty(B, dtype=F32, device=dev)
+        kn = torch.empty(P, dtype=F32, device=dev)
+        cnt = count.detach().float().contiguous() if contrastiv else None
+        ops.mvp_select(query, key_d, cnt, k, idx, dist, qn, kn, hist)
+        kcos = torch.empty(P, P, dtype=F32, device=dev) if contrastiv else None
+        raww = torch.empty(P, P, dtype=F32, device=dev) if contrastiv else None
+        rawgd = torch.empty(B, k, dtype=F32, device=dev)
+        coef = torch.empty(2, dtype=F32, device=dev)
+        loss = torch.empty(1, dtype=F32, device=dev)
+        ops.mvp_simloss(key_d, cnt, idx, dist, kn, contrastiv, kcos, rawgd, raww, coef, loss)
+        ctx.save_for_backward(key_d, query, idx, dist, qn, kn, rawgd, coef)
+        ctx.extra = (kcos, raww, bool(contrastiv))
+        ctx.mark_non_differentiable(idx, dist)
+        return loss.view(()), idx, dist
+
+    @staticmethod
+    def backward(ctx, dloss, _didx, _ddist):
+        key, query, idx, dist, qn, kn, rawgd, coef = ctx.saved_tensors
+        kcos, raww, contrastiv = ctx.extra
+        dkey = torch.empty_like(key)
+        ops.mvp_simloss_bwd(query, key, idx, dist, qn, kn, contrastiv, kcos, rawgd, raww, coef,
+                            dloss.reshape(1).float(), dkey)
+        return dkey, None, None, None, None, None
+
+
+def mvp_select_apply(key, query, count, k, contrastiv, hist=None):
+    """-> (similarity loss (0-dim), idx [B,k] int64, selected distances [B,k])."""
+    return _MvpSelectFn.apply(key, query, count, int(k), bool(contrastiv), hist)
+
+
+class _PoolGatherFn(torch.autograd.Function):
+    """table[idx] ([B,k,...]) or its mean over the k selections ([B,...]) for a [P,...] pool
+    table (models/mvp_clip.py:236-237) on lc_pool_gather / lc_pool_gather_bwd."""
+
+    @staticmethod
+    def forward(ctx, table, idx, mean):
+        t = table.detach()
+        P = t.shape[0]
+        t2 = t.reshape(P, -1)
+        B, k = idx.shape
+        out = torch.empty(B if mean else B * k, t2.shape[1], dtype=F32, device=t.device)
+        ops.pool_gather(t2, idx, out, mean)
+        ctx.save_for_backward(idx)
+        ctx.shape, ctx.mean = tuple(t.shape), bool(mean)
+        return out.view(*((B,) if mean else (B, k)), *t.shape[1:])
+
+    @staticmethod
+    def backward(ctx, g):
+        (idx,) = ctx.saved_tensors
+        B, k = idx.shape
+        P = ctx.shape[0]
+        g2 = g.contiguous().float().reshape(B if ctx.mean else B * k, -1)
+        dt = torch.empty(P, g2.shape[1], dtype=F32, device=g.device)
+        ops.pool_gather_bwd(idx, g2, dt, alpha=1.0 / k if ctx.mean else 1.0, shared_s=ctx.mean)
+        return dt.view(ctx.shape), None, None
+
+
+def pool_gather_apply(table, idx, mean=False):
+    return _PoolGatherFn.apply(table, idx.contiguous(), bool(mean))
+
+
+class MvpHeadState:
+    """Options and per-step results of the MVP head (lcclip.mvp_trainer). dp: an object with
+    all_sum(tensor) (lcclip.dp.ModuleDataParallel) or None; n_global: the global batch size."""
+
+    def __init__(self, use_afs=False, use_gsf=False, alpha=0.5, gamma=2.0, margin=0.5,
+                 compute_scores=False, dp=None):
+        self.use_afs, self.use_gsf = bool(use_afs), bool(use_gsf)
+        self.alpha, self.gamma, self.margin = float(alpha), float(gamma), float(margin)
+        self.compute_scores = bool(compute_scores)
+        self.dp = dp
+        self.logits = self.ign = self.cps = self.G = self.w = self.lbar = None
+        self.inputs = None  # (image features, text features, mask rows) of the last step
+
+    @property
+    def scoring(self):
+        return self.use_afs or self.use_gsf or self.compute_scores
+
+
+class _MvpHeadFn(torch.autograd.Function):
+    """methods/mvp_clip.py:256-280 (loss_fn without the similarity term) on the mvp.hip kernels:
+    normalise, [scores: head on the undivided features -> G (summed over ranks) -> ign, cps],
+    [AFS: divide by cps], masked logits + class mask -> mean NLL x GSF weight. Backward: the
+    gradients to the image features and to the selected pre-sigmoid mask rows (the text tower is
+    frozen in MVP: no text gradient)."""
+
+    @staticmethod
+    def forward(ctx, img_f, maskrows, txt_f, logit_scale, cmask, labels, st):
+        img_f = img_f.detach().contiguous().float()
+        txt_f = txt_f.detach().contiguous().float()
+        B, E = img_f.shape
+        C = txt_f.shape[0]
+        dev = img_f.device
+        mrows = None if maskrows is None else maskrows.detach().float().contiguous()
+        ls = logit_scale.detach().reshape(1).float().contiguous()
+        labels = labels.to(dev, torch.int64).contiguous()
+        new = lambda *s: torch.empty(*s, dtype=F32, device=dev)
+        img_n, txt_n, ni, nt = new(B, E), new(C, E), new(B), new(C)
+        ops.l2norm_rows(img_f, img_n, ni)
+        ops.l2norm_rows(txt_f, txt_n, nt)
+        logits, u, probs, nll, q1 = new(B, C), new(B, C), new(B, C), new(B), new(B)
+        dp = st.dp
+        n_global = B * (dp.world if dp is not None and dp.active else 1)
+        ign_sum = None
+        if st.scoring:
+            # the scores see the features as they are (methods/mvp_clip.py:257-262), AFS comes after
+            ops.mvp_head_fwd(img_n, txt_n, ls, mrows, cmask, labels, logits, u, probs, nll, q1)
+            G = new(C, E)
+            ops.mvp_score_g(img_n, probs, q1, mrows, ls, labels, 1.0 / n_global, G)
+            if dp is not None:
+                dp.all_sum(G)  # the reference scores against the gathered global batch
+            ign, cps = new(B), new(B)
+            ign_sum = new(1) if st.use_gsf else None
+            ops.mvp_score(img_n, txt_n, G, q1, mrows, ls, labels, st.margin, st.gamma, ign, cps,
+                          ign_sum)
+            if ign_sum is not None and dp is not None:
+                dp.all_sum(ign_sum)
+            st.ign, st.cps, st.G = ign, cps, G
+        if st.use_afs:
+            img_a, ni_a = new(B, E), new(B)
+            ops.mvp_afs(img_n, ni, st.cps, img_a, ni_a)
+            img_n, ni = img_a, ni_a
+        if st.use_afs or not st.scoring:
+            ops.mvp_head_fwd(img_n, txt_n, ls, mrows, cmask, labels, logits, u, probs, nll, q1)
+        loss, w, lbar = new(1), new(1), new(1)
+        ops.mvp_loss_mean(nll, ign_sum, st.alpha, n_global, loss, w, lbar)
+        st.logits, st.w, st.lbar = logits, w, lbar
+        st.inputs = (img_f, txt_f, mrows)
+        ctx.save_for_backward(probs, q1, u, labels, w, txt_n, img_n, ni, ls)
+        ctx.mrows = mrows
+        ctx.mark_non_differentiable(logits)
+        return loss.view(()), logits
+
+    @staticmethod
+    def backward(ctx, dloss, _dlogits):
+        probs, q1, u, labels, w, txt_n, img_n, ni, ls = ctx.saved_tensors
+        mrows = ctx.mrows
+        B, C = probs.shape
+        dlog = torch.empty_like(probs)
+        dmask = torch.empty_like(mrows) if mrows is not None and ctx.needs_input_grad[1] else None
+        ops.mvp_head_bwd(probs, q1, u, mrows, labels, w * dloss.reshape(1).float(), B, dlog, dmask)
+        d_img = torch.empty_like(img_n)
+        ops.head_feat_grad(dlog, C, 1, txt_n, img_n, ni, ls, d_img)
+        return d_img, dmask, None, None, None, None, None
+
+
+def mvp_head_apply(img_f, maskrows, txt_f, logit_scale, cmask, labels, state):
+    """-> (loss (0-dim) = mean NLL x GSF weight, masked logits [B,C]); state: MvpHeadState."""
+    return _MvpHeadFn.apply(img_f, maskrows, txt_f, logit_scale, cmask, labels, state)

@@ -12,8 +12,13 @@ e-prompt layers); backward returns the gradients of the appended prompt rows. Th
 frozen here (peft_encoder 'none'), so its features are cached per token tensor
 instead of being recomputed every step as the reference does.
 
-Selection, key distance, mask and the small [B, pool] / [B, C] tensors stay torch ops, as in the
-reference.
+pool_kernels (constructor argument and attribute, default False): with it off, selection, key
+distance, similarity loss, the pool gathers and the small [B, pool] / [B, C] tensors are torch
+ops, as in the reference. With it on (and the module on the GPU) the key distance, the top-k,
+the selection count, the similarity loss (plain and contrastive) and the e-prompt / mask gathers
+with their backward run on the mvp.hip kernels (lcclip.autograd.mvp_select_apply,
+pool_gather_apply): deterministic, no ATen arithmetic between the query pass and the prompt
+tower. lcclip.mvp_trainer.MVPTrainer (the training method, methods/mvp_clip.py) turns it on.
 """
 from __future__ import annotations
 
@@ -66,8 +71,9 @@ class CLIP_MVP(nn.Module):
                  num_classes: int = 100, lambd: float = 1.0, use_mask: bool = True,
                  use_contrastiv: bool = False, use_last_layer: bool = True,
                  model_name="ViT-B/16", device="cpu", tokenizer=None, arch_overrides=None,
-                 backbone=None, text_precision="fp16", **kwargs):
+                 backbone=None, text_precision="fp16", pool_kernels=False, **kwargs):
         super().__init__()
+        self.pool_kernels = bool(pool_kernels)
         self.features = torch.empty(0)
         self.keys = torch.empty(0)
         self.lambd = lambd
@@ -209,21 +215,8 @@ class CLIP_MVP(nn.Module):
     def prefix_tuning(self, x, g_prompt, e_prompt, **kwargs):
         raise NotImplementedError("prefix_tuning not implemented yet")  # mvp_clip.py:177-180
 
-    def forward_features(self, inputs, text_tokens=None, **kwargs):
-        """mvp_clip.py:182-264 -> (image features [B, E], text features [C, E], mask [B, C])."""
-        self.backbone.visual.eval()
-        if text_tokens is None:
-            text_tokens = self.text_tokens
-        text_features = self.encode_text_cached(text_tokens)
-        vis = self.backbone.visual
-        tower = vis.tower
-        with torch.no_grad():
-            x0, n, L, first = tower.embed_query(inputs)
-            stop = vis.layers if self.use_last_layer else vis.layers - 1
-            query = tower.query(x0, n, L, stop, first_ln1=first)
-        B = n
-        if self.training:
-            self.features = torch.cat((self.features, query.detach().cpu()), dim=0)
+    def _select_torch(self, query):
+        """mvp_clip.py:224-248 as torch ops -> (topk, e_prompts, pre-sigmoid mask rows)."""
         distance = 1 - F.cosine_similarity(query.unsqueeze(1), self.key, dim=-1)
         mass = (self.count + 1) if self.use_contrastiv else 1.0
         scaled_distance = distance * mass
@@ -240,10 +233,48 @@ class CLIP_MVP(nn.Module):
                                      1e-6).log()
         else:
             self.similarity_loss = distance.mean()
-        g_prompts = self.g_prompts[0].repeat(B, 1, 1)
+        num = None
         if self.training:
             with torch.no_grad():
                 num = topk.view(-1).bincount(minlength=self.e_prompts.size(0))
+        return topk, e_prompts, mask, num
+
+    def _select_kernels(self, query):
+        """The same on the mvp.hip kernels (pool_kernels): one selection launch (distance, top-k,
+        selected distances, bincount), the similarity loss, and the two gathers."""
+        num = None
+        if self.training:
+            num = torch.zeros(self.e_prompts.size(0), dtype=torch.int64, device=query.device)
+        self.similarity_loss, topk, _ = lc_autograd.mvp_select_apply(
+            self.key, query, self.count, self.selection_size, self.use_contrastiv, num)
+        e_prompts = lc_autograd.pool_gather_apply(self.e_prompts, topk).squeeze()
+        mask = lc_autograd.pool_gather_apply(self.mask, topk, mean=True).squeeze()
+        return topk, e_prompts, mask, num
+
+    def _features(self, inputs, text_tokens=None):
+        """forward_features up to the mask's sigmoid: (image features, text features, the selected
+        pre-sigmoid mask rows [B, n_classes] (squeezed as the reference does), C)."""
+        self.backbone.visual.eval()
+        if text_tokens is None:
+            text_tokens = self.text_tokens
+        text_features = self.encode_text_cached(text_tokens)
+        vis = self.backbone.visual
+        tower = vis.tower
+        with torch.no_grad():
+            x0, n, L, first = tower.embed_query(inputs)
+            stop = vis.layers if self.use_last_layer else vis.layers - 1
+            query = tower.query(x0, n, L, stop, first_ln1=first)
+        B = n
+        if self.training:
+            self.features = torch.cat((self.features, query.detach().cpu()), dim=0)
+        if self.pool_kernels and query.is_cuda:
+            topk, e_prompts, mask, num = self._select_kernels(query)
+        else:
+            topk, e_prompts, mask, num = self._select_torch(query)
+        self.last_topk = topk
+        g_prompts = self.g_prompts[0].repeat(B, 1, 1)
+        if num is not None:
+            with torch.no_grad():
                 dp = getattr(self, "_dp", None)
                 if dp is not None:  # one rank per GPU: count the global batch on every replica
                     dp.all_sum(num)
@@ -251,8 +282,13 @@ class CLIP_MVP(nn.Module):
         if e_prompts.dim() == 2:  # B == 1: the reference's squeeze() dropped the batch axis
             e_prompts = e_prompts.unsqueeze(0)
         x = self.prompt_func(x0, g_prompts.float(), e_prompts.float(), n=n, L=L)
-        mask = torch.sigmoid(mask) * 2.0
         C = (self.text_tokens if self.text_tokens is not None else text_tokens).shape[0]
+        return x, text_features, mask, C
+
+    def forward_features(self, inputs, text_tokens=None, **kwargs):
+        """mvp_clip.py:182-264 -> (image features [B, E], text features [C, E], mask [B, C])."""
+        x, text_features, mask, C = self._features(inputs, text_tokens)
+        mask = torch.sigmoid(mask) * 2.0
         return x, text_features, mask[..., :C]
 
     def forward_head(self, image_features, text_features=None, **kwargs):

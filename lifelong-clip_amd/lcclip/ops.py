@@ -630,6 +630,231 @@ def add_unscaled(y, x, scale):
     return y
 
 
+# ------------------------------------------------------------------ MVP-CLIP method (mvp.hip)
+I64 = torch.int64
+
+
+def _f32c(t, name, shape=None):
+    """A contiguous f32 tensor (of `shape` when given); None passes."""
+    if t is None:
+        return
+    if t.dtype != F32 or not t.is_contiguous():
+        raise TypeError(f"{name}: expected a contiguous float32 tensor, got {t.dtype} "
+                        f"strides {t.stride()}")
+    if shape is not None and tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{name}: expected shape {tuple(shape)}, got {tuple(t.shape)}")
+
+
+def _i64c(t, name, shape=None):
+    if t.dtype != I64 or not t.is_contiguous():
+        raise TypeError(f"{name}: expected a contiguous int64 tensor")
+    if shape is not None and tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{name}: expected shape {tuple(shape)}, got {tuple(t.shape)}")
+
+
+def mvp_select(query, key, count, k, idx, dist, qnorm, knorm, hist=None):
+    """lc_mvp_select: idx [B,k] int64 / dist [B,k] of the k smallest (count + 1)-scaled cosine
+    distances of query [B,W] to key [P,W]; qnorm [B], knorm [P]; hist [P] int64 += bincount."""
+    _rowmajor(query, F32, "query")
+    _rowmajor(key, F32, "key")
+    B, W = query.shape
+    P = key.shape[0]
+    if key.shape[1] != W:
+        raise ValueError(f"mvp_select: query {tuple(query.shape)} vs key {tuple(key.shape)}")
+    _f32c(count, "count", (P,))
+    _i64c(idx, "idx", (B, k))
+    _f32c(dist, "dist", (B, k))
+    _f32c(qnorm, "qnorm", (B,))
+    _f32c(knorm, "knorm", (P,))
+    if hist is not None:
+        _i64c(hist, "hist", (P,))
+    call("lc_mvp_select", stream_of(query), B, P, W, int(k), ptr(query), query.stride(0), ptr(key),
+         key.stride(0), ptr(count), ptr(idx), ptr(dist), ptr(qnorm), ptr(knorm), ptr(hist))
+
+
+def mvp_simloss(key, count, idx, dist, knorm, contrastiv, kcos, rawgd, raww, coef, loss):
+    """lc_mvp_simloss: loss [1] of the selection (plain mean, or the contrastive form, k = 1);
+    kcos / raww [P,P] (contrastive only), rawgd [B,k], coef [2] are kept for the backward."""
+    _rowmajor(key, F32, "key")
+    P, W = key.shape
+    B, k = idx.shape
+    _i64c(idx, "idx")
+    _f32c(dist, "dist", (B, k))
+    _f32c(rawgd, "rawgd", (B, k))
+    _f32c(coef, "coef", (2,))
+    _f32c(loss, "loss", (1,))
+    if contrastiv:
+        _f32c(count, "count", (P,))
+        _f32c(knorm, "knorm", (P,))
+        _f32c(kcos, "kcos", (P, P))
+        _f32c(raww, "raww", (P, P))
+    call("lc_mvp_simloss", stream_of(key), B, P, W, k, int(bool(contrastiv)), ptr(key),
+         key.stride(0), ptr(count), ptr(idx), ptr(dist), ptr(knorm), ptr(kcos), ptr(rawgd),
+         ptr(raww), ptr(coef), ptr(loss))
+
+
+def mvp_simloss_bwd(query, key, idx, dist, qnorm, knorm, contrastiv, kcos, rawgd, raww, coef,
+                    upstream, dkey):
+    """lc_mvp_simloss_bwd: dkey [P,W] = upstream[0] * dloss/dkey (upstream a device scalar)."""
+    _rowmajor(query, F32, "query")
+    _rowmajor(key, F32, "key")
+    _rowmajor(dkey, F32, "dkey")
+    B, W = query.shape
+    P = key.shape[0]
+    k = idx.shape[1]
+    if key.shape[1] != W or tuple(dkey.shape) != (P, W) or idx.shape[0] != B:
+        raise ValueError("mvp_simloss_bwd: shapes")
+    _i64c(idx, "idx")
+    _f32c(dist, "dist", (B, k))
+    _f32c(qnorm, "qnorm", (B,))
+    _f32c(knorm, "knorm", (P,))
+    _f32c(rawgd, "rawgd", (B, k))
+    _f32c(coef, "coef", (2,))
+    if upstream is not None and (upstream.dtype != F32 or upstream.numel() != 1):
+        raise ValueError("mvp_simloss_bwd: upstream must be one f32 element")
+    if contrastiv:
+        _f32c(kcos, "kcos", (P, P))
+        _f32c(raww, "raww", (P, P))
+    call("lc_mvp_simloss_bwd", stream_of(key), B, P, W, k, int(bool(contrastiv)), ptr(query),
+         query.stride(0), ptr(key), key.stride(0), ptr(idx), ptr(dist), ptr(qnorm), ptr(knorm),
+         ptr(kcos), ptr(rawgd), ptr(raww), ptr(coef), ptr(upstream), ptr(dkey), dkey.stride(0))
+
+
+def pool_gather(table, idx, out, mean=False):
+    """lc_pool_gather: out [B*k, R] = table[idx] or (mean) out [B, R] = mean_s table[idx[b, s]];
+    table [P, R] row-major."""
+    _rowmajor(table, F32, "table")
+    _i64c(idx, "idx")
+    B, k = idx.shape
+    P, R = table.shape
+    _f32c(out, "out", (B, R) if mean else (B * k, R))
+    call("lc_pool_gather", stream_of(table), B, k, P, R, ptr(table), table.stride(0), ptr(idx),
+         ptr(out), int(bool(mean)))
+
+
+def pool_gather_bwd(idx, g, dtable, alpha=1.0, shared_s=False):
+    """lc_pool_gather_bwd: dtable [P, R] = alpha * per-entry sums of g's rows ([B*k, R], or
+    [B, R] with shared_s), ascending (b, s) order."""
+    _i64c(idx, "idx")
+    _rowmajor(g, F32, "g")
+    _rowmajor(dtable, F32, "dtable")
+    B, k = idx.shape
+    P, R = dtable.shape
+    if tuple(g.shape) != ((B, R) if shared_s else (B * k, R)):
+        raise ValueError(f"pool_gather_bwd: g {tuple(g.shape)} for idx {tuple(idx.shape)}, R {R}")
+    ws = torch.empty(P + 1 + B * k, dtype=torch.int32, device=g.device)
+    call("lc_pool_gather_bwd", stream_of(g), B, k, P, R, ptr(idx), ptr(g), g.stride(0),
+         int(bool(shared_s)), float(alpha), ptr(dtable), dtable.stride(0), ptr(ws), ws.numel())
+
+
+def _head_shapes(img_n, txt_n, maskrows, labels):
+    _f32c(img_n, "img_n")
+    _f32c(txt_n, "txt_n")
+    B, E = img_n.shape
+    C = txt_n.shape[0]
+    if txt_n.shape[1] != E:
+        raise ValueError("img_n / txt_n widths differ")
+    if maskrows is not None:
+        _rowmajor(maskrows, F32, "maskrows")
+        if maskrows.shape[0] != B or maskrows.shape[1] < C:
+            raise ValueError(f"maskrows {tuple(maskrows.shape)}: need [{B}, >= {C}]")
+    _i64c(labels, "labels", (B,))
+    return B, C, E
+
+
+def mvp_head_fwd(img_n, txt_n, logit_scale, maskrows, cmask, labels, logits, u, probs, nll, q1):
+    """lc_mvp_head_fwd: masked logits (+ the 0 / -inf class mask), softmax, per-row NLL and
+    1 - p[y]; u the unmasked logits (for the mask gradient)."""
+    B, C, E = _head_shapes(img_n, txt_n, maskrows, labels)
+    _f32c(cmask, "cmask", (C,))
+    for t, n in ((logits, "logits"), (u, "u"), (probs, "probs")):
+        _f32c(t, n, (B, C))
+    _f32c(nll, "nll", (B,))
+    _f32c(q1, "q1", (B,))
+    call("lc_mvp_head_fwd", stream_of(img_n), B, C, E, ptr(img_n), ptr(txt_n), ptr(logit_scale),
+         ptr(maskrows), maskrows.stride(0) if maskrows is not None else 0, ptr(cmask), ptr(labels),
+         ptr(logits), ptr(u), ptr(probs), ptr(nll), ptr(q1))
+
+
+def mvp_loss_mean(nll, gsf_sum, alpha, n_global, loss, w, lbar):
+    """lc_mvp_loss_mean: lbar = mean nll, w = (1 - alpha) + alpha * gsf_sum / n_global (1 when
+    gsf_sum is None), loss = lbar * w; all [1] device scalars."""
+    _f32c(nll, "nll")
+    for t, n in ((gsf_sum, "gsf_sum"), (loss, "loss"), (w, "w"), (lbar, "lbar")):
+        _f32c(t, n, (1,))
+    call("lc_mvp_loss_mean", stream_of(nll), nll.numel(), ptr(nll), ptr(gsf_sum), float(alpha),
+         1.0 / float(n_global), ptr(loss), ptr(w), ptr(lbar))
+
+
+def mvp_score_g(img_n, probs, q1, maskrows, logit_scale, labels, scale, G):
+    """lc_mvp_score_g: G [C,E], the batch gradient to the text features in closed form."""
+    B, E = img_n.shape
+    C = probs.shape[1]
+    _f32c(img_n, "img_n")
+    _f32c(probs, "probs", (B, C))
+    _f32c(q1, "q1", (B,))
+    _f32c(G, "G", (C, E))
+    _i64c(labels, "labels", (B,))
+    if maskrows is not None:
+        _rowmajor(maskrows, F32, "maskrows")
+        if maskrows.shape[0] != B or maskrows.shape[1] < C:
+            raise ValueError("maskrows shape")
+    call("lc_mvp_score_g", stream_of(img_n), B, C, E, ptr(img_n), ptr(probs), ptr(q1),
+         ptr(maskrows), maskrows.stride(0) if maskrows is not None else 0, ptr(logit_scale),
+         ptr(labels), float(scale), ptr(G))
+
+
+def mvp_score(img_n, txt_n, G, q1, maskrows, logit_scale, labels, margin, gamma, ign, cps,
+              ign_sum=None):
+    """lc_mvp_score: ign [B], cps [B] and ign_sum [1] = sum ign^gamma."""
+    B, C, E = _head_shapes(img_n, txt_n, maskrows, labels)
+    _f32c(G, "G", (C, E))
+    _f32c(q1, "q1", (B,))
+    _f32c(ign, "ign", (B,))
+    _f32c(cps, "cps", (B,))
+    _f32c(ign_sum, "ign_sum", (1,))
+    call("lc_mvp_score", stream_of(img_n), B, C, E, ptr(img_n), ptr(txt_n), ptr(G), ptr(q1),
+         ptr(maskrows), maskrows.stride(0) if maskrows is not None else 0, ptr(logit_scale),
+         ptr(labels), float(margin), float(gamma), ptr(ign), ptr(cps), ptr(ign_sum))
+
+
+def mvp_afs(img_n, norms, cps, out_n, out_norms):
+    """lc_mvp_afs: the normalised feature and effective norm after dividing by cps."""
+    B, E = img_n.shape
+    _f32c(img_n, "img_n")
+    _f32c(norms, "norms", (B,))
+    _f32c(cps, "cps", (B,))
+    _f32c(out_n, "out_n", (B, E))
+    _f32c(out_norms, "out_norms", (B,))
+    call("lc_mvp_afs", stream_of(img_n), B, E, ptr(img_n), ptr(norms), ptr(cps), ptr(out_n),
+         ptr(out_norms))
+
+
+def mvp_head_bwd(probs, q1, u, maskrows, labels, w, n_batch, dlog, dmask=None):
+    """lc_mvp_head_bwd: dlog [B,C] to the unmasked logits and dmask [B,NC] to the pre-sigmoid
+    mask rows, for dz = w (p - onehot) / n_batch."""
+    B, C = probs.shape
+    _f32c(probs, "probs")
+    _f32c(q1, "q1", (B,))
+    _f32c(u, "u", (B, C))
+    _f32c(dlog, "dlog", (B, C))
+    _i64c(labels, "labels", (B,))
+    NC = C
+    if maskrows is not None:
+        _rowmajor(maskrows, F32, "maskrows")
+        if maskrows.shape[0] != B or maskrows.shape[1] < C:
+            raise ValueError("maskrows shape")
+    if dmask is not None:
+        _rowmajor(dmask, F32, "dmask")
+        NC = dmask.shape[1]
+        if maskrows is None or dmask.shape[0] != B or NC < C:
+            raise ValueError("dmask shape")
+    _f32c(w, "w", (1,))
+    call("lc_mvp_head_bwd", stream_of(probs), B, C, NC, ptr(probs), ptr(q1), ptr(u), ptr(maskrows),
+         maskrows.stride(0) if maskrows is not None else 0, ptr(labels), ptr(w),
+         1.0 / float(n_batch), ptr(dlog), ptr(dmask), dmask.stride(0) if dmask is not None else 0)
+
+
 def device_cu_count(device):
     """Compute units of a HIP device (lc_device_cu_count)."""
     import ctypes
