@@ -281,6 +281,24 @@ int lc_attn_bwd(hipStream_t stream, int n_seq, int L, int H, const void* qkv, lo
  * (dQ, then dK / dV, in one workgroup with 59 KB of LDS: two workgroups per CU; L <= 224).
  * All forms compute the same dq|dk|dv up to f32 summation order. -1 for other values. */
 int lc_attn_bwd_set_form(int form);
+/* One query row per sequence (the image tower's last block: its head reads the CLS row only,
+ * model.py:782). 0 <= row < L <= 256; causal: keys <= row.
+ * lc_attn_row_fwd: O_row [n_seq, ldo] and lse_row [n_seq*H] (log2 domain) are row `row` of what
+ * lc_attn_fwd returns, bit for bit (compact: one output row per sequence).
+ * lc_attn_row_bwd: lc_attn_bwd with dO zero on every other row, from the compact O_row / dO_row
+ * / lse_row. Writes all L rows of dq | dk | dv of every sequence (dq zero off `row`; dk, dv zero
+ * for the keys the row does not see), so the QKV input-gradient GEMM after it is unchanged.
+ * ldq, ldo, lddq % 8 == 0; O_row, dO_row, dqkv 16-B aligned. */
+int lc_attn_row_fwd(hipStream_t stream, int n_seq, int L, int H, const void* qkv, long ldq,
+                    int row, void* O_row, long ldo, float* lse_row, int causal);
+int lc_attn_row_bwd(hipStream_t stream, int n_seq, int L, int H, const void* qkv, long ldq,
+                    int row, const void* O_row, const void* dO_row, long ldo,
+                    const float* lse_row, void* dqkv, long lddq, int causal);
+int lc_attn_row_fwd_f16(hipStream_t stream, int n_seq, int L, int H, const void* qkv, long ldq,
+                        int row, void* O_row, long ldo, float* lse_row, int causal);
+int lc_attn_row_bwd_f16(hipStream_t stream, int n_seq, int L, int H, const void* qkv, long ldq,
+                        int row, const void* O_row, const void* dO_row, long ldo,
+                        const float* lse_row, void* dqkv, long lddq, int causal);
 /* The backward with dq|dk|dv written as the A operand of the fp8 QKV input-gradient GEMM
  * (lc_gemm_nt_fp8): e4m3 codes dqkv [n_seq*L, lddq BYTES] (lddq % 16 == 0, 16-B aligned) + E8M0
  * scales q_scale [3*H*64/128][q_rows][4] (q_rows = n_seq*L rounded up to 256), bit-identical to
@@ -399,6 +417,42 @@ int lc_adapter_ln_fwd(hipStream_t stream, int M, int D, const void* z, long ldz,
                       const float* resid, float* xout, long ldx, void* hout,
                       const float* gamma, const float* beta, void* y, long ldy, float* mean,
                       float* rstd);
+
+/* The adapter forwards on rows gathered from a larger launch: row m draws the dropout mask of
+ * row m * row_mul + row_add (row_mul >= 1, row_add >= 0), so the compact rows keep the mask and
+ * hence the bits they had there (the arithmetic is row-local). The image tower's last block
+ * runs them on its CLS rows only, row_mul = L (model.py:782 reads no other row of its output).
+ * Everything else as lc_adapter_fwd / lc_adapter_ln_fwd / lc_adapter_ln_fwd_x16. */
+int lc_adapter_fwd_rows(hipStream_t stream, int M, int D, const void* z, long ldz, const void* Wd,
+                        const float* bd, const void* Wu, const float* bu, float scale, float keep,
+                        unsigned long long seed, const unsigned long long* seed_dev,
+                        const float* resid, float* xout, long ldx, void* h, long row_mul,
+                        long row_add);
+int lc_adapter_ln_fwd_rows(hipStream_t stream, int M, int D, const void* z, long ldz,
+                           const void* Wd, const float* bd, const void* Wu, const float* bu,
+                           float scale, float keep, unsigned long long seed,
+                           const unsigned long long* seed_dev, const float* resid, float* xout,
+                           long ldx, void* hout, const float* gamma, const float* beta, void* y,
+                           long ldy, float* mean, float* rstd, long row_mul, long row_add);
+int lc_adapter_ln_fwd_rows_x16(hipStream_t stream, int M, int D, const void* z, long ldz,
+                               const void* Wd, const float* bd, const void* Wu, const float* bu,
+                               float scale, float keep, unsigned long long seed,
+                               const unsigned long long* seed_dev, const void* resid, void* xout,
+                               long ldx, void* hout, const float* gamma, const float* beta,
+                               void* y, long ldy, float* mean, float* rstd, long row_mul,
+                               long row_add);
+int lc_adapter_fwd_rows_f16(hipStream_t stream, int M, int D, const void* z, long ldz,
+                            const void* Wd, const float* bd, const void* Wu, const float* bu,
+                            float scale, float keep, unsigned long long seed,
+                            const unsigned long long* seed_dev, const float* resid, float* xout,
+                            long ldx, void* h, long row_mul, long row_add);
+int lc_adapter_ln_fwd_rows_f16(hipStream_t stream, int M, int D, const void* z, long ldz,
+                               const void* Wd, const float* bd, const void* Wu, const float* bu,
+                               float scale, float keep, unsigned long long seed,
+                               const unsigned long long* seed_dev, const float* resid,
+                               float* xout, long ldx, void* hout, const float* gamma,
+                               const float* beta, void* y, long ldy, float* mean, float* rstd,
+                               long row_mul, long row_add);
 
 /* Row-local adapter backward: dpre (bf16 [M,64]) and dz = gout + dpre Wd (bf16; dz = NULL
  * computes dpre only).

@@ -122,11 +122,18 @@ constexpr int V_STRIDE = 160;  // bytes per V row in the forward's plain V image
 // (a first pass of S = K Q^T for the max alone): a third fewer MFMAs and K reads, image forward
 // 103.4 -> 94.8 us standalone (profiles/r03/s2/u_ab_attn_online.txt). LCCLIP_ATTN_FWD_ONLINE=0
 // selects the two-pass form (A/Bs).
-template <int NQB, bool ONLINE = true>
+//
+// ROW: one query row per sequence (the image tower's last block: its head reads the CLS row only,
+// model.py:782). The same instructions on the same operands as the full launch — every wave
+// stages K / V, then only the wave that owns query `row` goes on — so O_row [n_seq, ldo] and
+// lse_row [n_seq*H] are bit for bit row `row` of the full launch's O and lse (compact: one output
+// row per sequence). K and V are still read whole; the Q reads, 6/7 of the MFMA / exp work and
+// the O stores go.
+template <int NQB, bool ONLINE = true, bool ROW = false>
 __global__ void __launch_bounds__(64 * NQB, 4)
 attn_fwd_kernel(int L, int H, int D, const bf16_t* __restrict__ qkv, long ldq,
                 bf16_t* __restrict__ O, long ldo, float* __restrict__ lse, int causal,
-                float scale) {
+                float scale, int row = 0) {
   constexpr int LP = 32 * NQB;
   constexpr int NTH = 64 * NQB;
   __shared__ __attribute__((aligned(16))) char smem[LP * 128 + LP * V_STRIDE];
@@ -170,6 +177,9 @@ attn_fwd_kernel(int L, int H, int D, const bf16_t* __restrict__ qkv, long ldq,
     *reinterpret_cast<uint4*>(Vs + r * V_STRIDE + ch * 16) = vv[i];
   }
   __syncthreads();
+  if constexpr (ROW) {
+    if (w != (row >> 5)) return;  // (no barrier below)
+  }
 
   const char* k0 = Ks + row_off(t, g, 0);
   const char* k1 = Ks + row_off(t, g, 1);
@@ -280,7 +290,7 @@ attn_fwd_kernel(int L, int H, int D, const bf16_t* __restrict__ qkv, long ldq,
     l += __shfl_xor(l, 16);
     l += __shfl_xor(l, 32);
     const int q = qb + qt * 16 + t;
-    if (q < L) {
+    if (ROW ? q == row : q < L) {
       const float inv = 1.0f / l;
       uint2 x[4];
 #pragma unroll
@@ -288,8 +298,8 @@ attn_fwd_kernel(int L, int H, int D, const bf16_t* __restrict__ qkv, long ldq,
         const f32x4 o = Oa[dt][qt];
         x[dt] = uint2{pack2bf(o[0] * inv, o[1] * inv), pack2bf(o[2] * inv, o[3] * inv)};
       }
-      store_row64(O + (base + q) * ldo + h * 64, g, x);
-      if (g == 0) lse[(long)nh * L + q] = mx[qt] + __log2f(l);
+      store_row64(O + (ROW ? (long)n : base + q) * ldo + h * 64, g, x);
+      if (g == 0) lse[ROW ? (long)nh : (long)nh * L + q] = mx[qt] + __log2f(l);
     }
   }
 }
@@ -1235,6 +1245,128 @@ attn_bwd2_kernel(int L, int H, int D, const bf16_t* __restrict__ qkv, long ldq,
   }
 }
 
+// -------------------------------------------------- one query row per sequence: the backward
+// The image tower's head reads the CLS row of the last block only (model.py:782), so that block's
+// attention has one live query per (sequence, head) (forward: attn_fwd_kernel<.., ROW>). Its
+// backward is L dot products of 64 and rank-1 updates: memory-bound (K and V of every key are
+// read, all of dq | dk | dv written), plain f32 VALU, no MFMA.
+// One workgroup of 4 waves per (sequence, head); 8 lanes share a key row (lane ch holds its 16-B
+// chunk ch), 32 rows per pass, ROW_IT passes cover L <= 256. Every K / V load of a lane is issued
+// before its first use; rows >= L read zero through the sequence's descriptor and their stores
+// are dropped by its range check.
+constexpr int ROW_NTH = 256;
+constexpr int ROW_IT = 8;
+
+LC_DEV void unpack8(uint4 u, float (&f)[8]) {
+  const uint32_t w[4] = {u.x, u.y, u.z, u.w};
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    f[2 * k] = bf2f(w[k] & 0xffff);
+    f[2 * k + 1] = bf2f(w[k] >> 16);
+  }
+}
+LC_DEV float dot8(const float (&a)[8], const float (&b)[8]) {
+  float s = 0.f;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) s = __builtin_fmaf(a[j], b[j], s);
+  return s;
+}
+// sum over the 8 lanes of a row (all of them get it) / over the 8 rows of a wave's pass
+LC_DEV float sum_row8(float v) {
+  v += __shfl_xor(v, 1);
+  v += __shfl_xor(v, 2);
+  v += __shfl_xor(v, 4);
+  return v;
+}
+LC_DEV float sum_rows8(float v) {
+  v += __shfl_xor(v, 8);
+  v += __shfl_xor(v, 16);
+  v += __shfl_xor(v, 32);
+  return v;
+}
+typedef unsigned int row_v4u __attribute__((ext_vector_type(4)));
+
+// dO is zero off `row`: dv_j = p_j dO, dk_j = scale dS_j q, dq_row = scale sum_j dS_j k_j with
+// dS_j = p_j (dO . v_j - dO . O); every other dq row, and dk / dv of the keys the row does not
+// see, are written as zeros (all L rows of the sequence's dq | dk | dv are written).
+__global__ void __launch_bounds__(ROW_NTH)
+attn_row_bwd_kernel(int L, int H, int D, const bf16_t* __restrict__ qkv, long ldq, int row,
+                    const bf16_t* __restrict__ O, const bf16_t* __restrict__ dO, long ldo,
+                    const float* __restrict__ lse, bf16_t* __restrict__ dqkv, long lddq, int causal,
+                    float scale) {
+  __shared__ float red_q[4][64];
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int ch = tid & 7, r0 = tid >> 3;
+  const int nh = blockIdx.x, n = nh / H, h = nh % H;
+  const float c = scale * LOG2E;
+  const auto rq = seq_rsrc(qkv, (long)n * L, ldq * 2, L);
+  const auto rs = seq_rsrc(dqkv, (long)n * L, lddq * 2, L);
+  const int cb = (h * 64 + ch * 8) * 2;
+  uint4 kv[ROW_IT], vv[ROW_IT];
+#pragma unroll
+  for (int i = 0; i < ROW_IT; ++i) {
+    const int off = (r0 + 32 * i) * (int)ldq * 2 + cb;
+    kv[i] = seq_ld16(rq, off + D * 2);
+    vv[i] = seq_ld16(rq, off + D * 4);
+  }
+  float qf[8], df[8], of[8];
+  unpack8(seq_ld16(rq, row * (int)ldq * 2 + cb), qf);
+  unpack8(*reinterpret_cast<const uint4*>(dO + (long)n * ldo + h * 64 + ch * 8), df);
+  unpack8(*reinterpret_cast<const uint4*>(O + (long)n * ldo + h * 64 + ch * 8), of);
+  const float delta = sum_row8(dot8(df, of));
+  const float nl = -lse[nh];
+  const int last = causal ? row : L - 1;
+  const int oob = L * (int)lddq * 2;  // an offset the descriptor's range check drops
+
+  float dqa[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) dqa[j] = 0.f;
+#pragma unroll
+  for (int i = 0; i < ROW_IT; ++i) {
+    const int r = r0 + 32 * i;
+    float kf[8], vf[8];
+    unpack8(kv[i], kf);
+    unpack8(vv[i], vf);
+    const float sc = sum_row8(dot8(qf, kf));
+    const float dp = sum_row8(dot8(df, vf));
+    const bool seen = r <= last;
+    const float p = seen ? ex2(__builtin_fmaf(sc, c, nl)) : 0.f;
+    // attn_bwd_kernel's rounding points: P and dS enter their products in the storage type
+    const float ds = seen ? bf2f(f2bf(p * (dp - delta))) : 0.f;
+    const float pr = bf2f(f2bf(p));
+    const float dss = ds * scale;
+    row_v4u wk, wv;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      dqa[2 * k] = __builtin_fmaf(ds, kf[2 * k], dqa[2 * k]);
+      dqa[2 * k + 1] = __builtin_fmaf(ds, kf[2 * k + 1], dqa[2 * k + 1]);
+      wk[k] = seen ? pack2bf(dss * qf[2 * k], dss * qf[2 * k + 1]) : 0u;
+      wv[k] = seen ? pack2bf(pr * df[2 * k], pr * df[2 * k + 1]) : 0u;
+    }
+    const int off = r * (int)lddq * 2 + cb;
+    __builtin_amdgcn_raw_buffer_store_b128(wk, rs, off + D * 2, 0, 0);
+    __builtin_amdgcn_raw_buffer_store_b128(wv, rs, off + D * 4, 0, 0);
+    // dq: zero off the row (the row itself is stored after the reduction, by the same lanes)
+    __builtin_amdgcn_raw_buffer_store_b128(row_v4u{0u, 0u, 0u, 0u}, rs, r != row ? off : oob, 0, 0);
+  }
+#pragma unroll
+  for (int j = 0; j < 8; ++j) dqa[j] = sum_rows8(dqa[j]);
+  if (lane < 8) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) red_q[w][ch * 8 + j] = dqa[j];
+  }
+  __syncthreads();
+  if (r0 == (row & 31)) {
+    float x[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j)
+      x[j] = ((red_q[0][ch * 8 + j] + red_q[1][ch * 8 + j]) +
+              (red_q[2][ch * 8 + j] + red_q[3][ch * 8 + j])) * scale;
+    *reinterpret_cast<uint4*>(dqkv + ((long)n * L + row) * lddq + h * 64 + ch * 8) =
+        uint4{pack2bf(x[0], x[1]), pack2bf(x[2], x[3]), pack2bf(x[4], x[5]), pack2bf(x[6], x[7])};
+  }
+}
+
 // workgroups of a persistent launch: as many as fit on the chip at once (LDS-limited) when there
 // are many items per workgroup (L = 197: 3072 items, 12 per workgroup), else one per item
 int persistent_grid(int items, int lds_bytes) {
@@ -1251,6 +1383,14 @@ int persistent_grid(int items, int lds_bytes) {
   const int g = cus * per_cu;
   // a few items per workgroup would leave a ragged last round: one item each (no pipelining)
   return items < 4 * g ? items : g;
+}
+
+bool attn_fwd_online() {  // DIAG builds: LCCLIP_ATTN_FWD_ONLINE=0 selects the two-pass forward
+  static const bool online = [] {
+    const char* e = lc_diag_env("LCCLIP_ATTN_FWD_ONLINE");
+    return !(e && e[0] == '0');
+  }();
+  return online;
 }
 
 // lc_attn_bwd_set_form: 0 automatic, else one of these
@@ -1278,10 +1418,7 @@ int lc_attn_fwd(hipStream_t st, int n_seq, int L, int H, const void* qkv, long l
   const int nqb = (L + 31) / 32;
   dim3 grid(n_seq * H);
   const float scale = 0.125f;  // 64^-0.5
-  static const bool online = [] {
-    const char* e = lc_diag_env("LCCLIP_ATTN_FWD_ONLINE");
-    return !(e && e[0] == '0');
-  }();
+  const bool online = attn_fwd_online();
   switch (nqb) {
 #define LC_AF(Q)                                                                                \
   case Q:                                                                                      \
@@ -1397,6 +1534,49 @@ int lc_attn_bwd(hipStream_t st, int n_seq, int L, int H, const void* qkv, long l
     default:
       return LC_EINVAL;
   }
+  LC_LAUNCH_RET();
+}
+
+int lc_attn_row_fwd(hipStream_t st, int n_seq, int L, int H, const void* qkv, long ldq, int row,
+                    void* O_row, long ldo, float* lse_row, int causal) {
+  LC_CHECK_ARG(n_seq > 0 && L > 0 && L <= 32 * ROW_IT && H > 0 && row >= 0 && row < L);
+  LC_CHECK_ARG(ldq >= 3 * H * 64 && ldo >= H * 64 && ldq % 8 == 0 && ldo % 8 == 0 &&
+               ((uintptr_t)O_row & 15) == 0 && (long)L * ldq * 2 < 0x7fffffffL);
+  const int D = H * 64;
+  dim3 grid(n_seq * H);
+  const float scale = 0.125f;
+  const bool online = attn_fwd_online();
+  switch ((L + 31) / 32) {
+#define LC_AFR(Q)                                                                               \
+  case Q:                                                                                      \
+    if (online)                                                                                \
+      hipLaunchKernelGGL((attn_fwd_kernel<Q, true, true>), grid, dim3(64 * Q), 0, st, L, H, D, \
+                         (const bf16_t*)qkv, ldq, (bf16_t*)O_row, ldo, lse_row, causal, scale, \
+                         row);                                                                 \
+    else                                                                                       \
+      hipLaunchKernelGGL((attn_fwd_kernel<Q, false, true>), grid, dim3(64 * Q), 0, st, L, H, D,\
+                         (const bf16_t*)qkv, ldq, (bf16_t*)O_row, ldo, lse_row, causal, scale, \
+                         row);                                                                 \
+    break;
+    LC_AFR(1) LC_AFR(2) LC_AFR(3) LC_AFR(4) LC_AFR(5) LC_AFR(6) LC_AFR(7) LC_AFR(8)
+#undef LC_AFR
+    default:
+      return LC_EINVAL;
+  }
+  LC_LAUNCH_RET();
+}
+
+int lc_attn_row_bwd(hipStream_t st, int n_seq, int L, int H, const void* qkv, long ldq, int row,
+                    const void* O_row, const void* dO_row, long ldo, const float* lse_row,
+                    void* dqkv, long lddq, int causal) {
+  LC_CHECK_ARG(n_seq > 0 && L > 0 && L <= 32 * ROW_IT && H > 0 && row >= 0 && row < L);
+  LC_CHECK_ARG(ldq >= 3 * H * 64 && ldo >= H * 64 && lddq >= 3 * H * 64 && ldq % 8 == 0 &&
+               ldo % 8 == 0 && lddq % 8 == 0 && ((uintptr_t)O_row & 15) == 0 &&
+               ((uintptr_t)dO_row & 15) == 0 && ((uintptr_t)dqkv & 15) == 0 &&
+               (long)L * ldq * 2 < 0x7fffffffL && (long)L * lddq * 2 < 0x7fffffffL);
+  hipLaunchKernelGGL(attn_row_bwd_kernel, dim3(n_seq * H), dim3(ROW_NTH), 0, st, L, H, H * 64,
+                     (const bf16_t*)qkv, ldq, row, (const bf16_t*)O_row, (const bf16_t*)dO_row,
+                     ldo, lse_row, (bf16_t*)dqkv, lddq, causal, 0.125f);
   LC_LAUNCH_RET();
 }
 

@@ -255,6 +255,8 @@ LC_DEV void store_tile(f32x4 (&acc)[TM][TN], char* smem, int smem_bytes, int m0,
   uint64_t seed = ep.seed;
   if constexpr (EPI == EPI_AD_DOWN)
     if (ep.seed_dev) seed += *ep.seed_dev * 0xD1B54A32D192ED03ull;
+  // dropout row id m * row_mul + row_add (scalars; row_mul 0: the row itself)
+  const long row_mul = ep.row_mul ? ep.row_mul : 1;
 #pragma unroll
   for (int pass = 0; pass < WT_M / PASS; ++pass) {
 #pragma unroll
@@ -329,7 +331,7 @@ LC_DEV void store_tile(f32x4 (&acc)[TM][TN], char* smem, int smem_bytes, int m0,
           store_bf(rs0, ldo0, m, w);
       } else if constexpr (EPI == EPI_AD_DOWN) {
 #pragma unroll
-        for (int i = 0; i < CPL; ++i) w[i] = fmaxf(v[i], 0.f) * drop_mul(seed, m, n + i, ep.keep);
+        for (int i = 0; i < CPL; ++i) w[i] = fmaxf(v[i], 0.f) * drop_mul(seed, m * row_mul + ep.row_add, n + i, ep.keep);
         store_bf(rs0, ldo0, m, w);
       } else if constexpr (EPI == EPI_AD_UP) {
 #pragma unroll

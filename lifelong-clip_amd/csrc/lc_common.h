@@ -175,6 +175,9 @@ struct EpiParams {
   uint8_t* q_scale;  // fp8-output epilogues: E8M0 scales of the fp8 output ([N/128][q_rows][4])
   long q_rows;       // padded row count of that scale buffer
   int group_m;       // 256x256 GEMMs: tile raster groups of group_m row panels (0/1: row-major)
+  // EPI_AD_DOWN: row m draws the dropout mask of row m * row_mul + row_add (row_mul 0: of row m;
+  // compact rows gathered from a larger launch keep the mask they had there)
+  long row_mul, row_add;
 };
 
 // fp8 operand scales of a block-scaled GEMM (see fp8_scale_index)

@@ -7,6 +7,8 @@
 #define lc_attn_bwd_fp8 lc_attn_bwd_fp8_f16
 #define lc_attn_bwd lc_attn_bwd_f16
 #define lc_attn_bwd_set_form lc_attn_bwd_set_form_f16
+#define lc_attn_row_fwd lc_attn_row_fwd_f16
+#define lc_attn_row_bwd lc_attn_row_bwd_f16
 #define lc_gemm_nt_ex lc_gemm_nt_ex_f16
 #define lc_gemm_nt lc_gemm_nt_f16
 #define lc_gemm_nt_ws lc_gemm_nt_ws_f16
@@ -35,6 +37,8 @@
 #define lc_lora_grad_ws lc_lora_grad_ws_f16
 #define lc_adapter_fwd lc_adapter_fwd_f16
 #define lc_adapter_ln_fwd lc_adapter_ln_fwd_f16
+#define lc_adapter_fwd_rows lc_adapter_fwd_rows_f16
+#define lc_adapter_ln_fwd_rows lc_adapter_ln_fwd_rows_f16
 #define lc_adapter_bwd_set_form lc_adapter_bwd_set_form_f16
 #define lc_adapter_bwd lc_adapter_bwd_f16
 #define lc_check_finite lc_check_finite_f16

@@ -943,7 +943,8 @@ adapter_ln_fwd_kernel(int M, const bf16_t* __restrict__ z, long ldz, const bf16_
                       const XT* __restrict__ resid, XT* __restrict__ xout, long ldx,
                       bf16_t* __restrict__ hout, const float* __restrict__ gamma,
                       const float* __restrict__ beta, bf16_t* __restrict__ y, long ldy,
-                      float* __restrict__ mean_out, float* __restrict__ rstd_out) {
+                      float* __restrict__ mean_out, float* __restrict__ rstd_out, long row_mul,
+                      long row_add) {
   constexpr int XB = (int)sizeof(XT);
   using L = AdLnLay<D, XB>;
   constexpr int KS = L::KS, NU = L::NU;
@@ -1085,7 +1086,7 @@ adapter_ln_fwd_kernel(int M, const bf16_t* __restrict__ z, long ldz, const bf16_
       for (int rr = 0; rr < 4; ++rr) {
         const int m = 4 * g + rr;
         float v = pd[rr] + red[m * 64 + j];
-        v = fmaxf(v + prm[3 * D + j], 0.f) * drop_mul(seed, (long)(r0 + m), j, keep);
+        v = fmaxf(v + prm[3 * D + j], 0.f) * drop_mul(seed, (long)(r0 + m) * row_mul + row_add, j, keep);
         hs[m * 64 + j] = f2bf(v);
       }
     }
@@ -1402,13 +1403,16 @@ int lc_lora_grad_ws_unscaled(hipStream_t st, int M, int N, int K, int r, const v
 // are staged once per workgroup by global_load_lds instead of being re-read by every wave):
 //   h    = drop(relu(z Wd^T + bd))                 [M,64]  N = 64,  K = D
 //   xout = resid + z + scale * (h Wu^T + bu)       [M,D]   N = D,   K = 64
-int lc_adapter_fwd(hipStream_t st, int M, int D, const void* z, long ldz, const void* Wd,
-                   const float* bd, const void* Wu, const float* bu, float scale, float keep,
-                   unsigned long long seed, const unsigned long long* seed_dev,
-                   const float* resid, float* xout, long ldx, void* hout) {
+static int adapter_fwd(hipStream_t st, int M, int D, const void* z, long ldz, const void* Wd,
+                       const float* bd, const void* Wu, const float* bu, float scale, float keep,
+                       unsigned long long seed, const unsigned long long* seed_dev,
+                       const float* resid, float* xout, long ldx, void* hout, long row_mul,
+                       long row_add) {
   LC_CHECK_ARG(M > 0 && D % 64 == 0 && ldz % 8 == 0 && ldx % 4 == 0);
-  LC_CHECK_ARG(keep > 0.f && keep <= 1.f);
+  LC_CHECK_ARG(keep > 0.f && keep <= 1.f && row_mul >= 1 && row_add >= 0);
   EpiParams ep{z, ldz, scale, keep, (uint64_t)seed, nullptr, seed_dev};
+  ep.row_mul = row_mul;
+  ep.row_add = row_add;
   int rc = lc_gemm_nt_ex(st, 8 /*EPI_AD_DOWN*/, M, AD_H, D, z, ldz, Wd, D, bd, 1.0f, hout, AD_H,
                          nullptr, 0, nullptr, 0, ep);
   if (rc) return rc;
@@ -1416,13 +1420,34 @@ int lc_adapter_fwd(hipStream_t st, int M, int D, const void* z, long ldz, const 
                        nullptr, 0, resid, ldx, ep);
 }
 
+int lc_adapter_fwd(hipStream_t st, int M, int D, const void* z, long ldz, const void* Wd,
+                   const float* bd, const void* Wu, const float* bu, float scale, float keep,
+                   unsigned long long seed, const unsigned long long* seed_dev,
+                   const float* resid, float* xout, long ldx, void* hout) {
+  return adapter_fwd(st, M, D, z, ldz, Wd, bd, Wu, bu, scale, keep, seed, seed_dev, resid, xout,
+                     ldx, hout, 1, 0);
+}
+
+// The _rows forms: row m draws the dropout mask of row m * row_mul + row_add (rows gathered
+// from a larger launch keep the mask they had there: the last block's CLS rows, row_mul = L).
+int lc_adapter_fwd_rows(hipStream_t st, int M, int D, const void* z, long ldz, const void* Wd,
+                        const float* bd, const void* Wu, const float* bu, float scale, float keep,
+                        unsigned long long seed, const unsigned long long* seed_dev,
+                        const float* resid, float* xout, long ldx, void* hout, long row_mul,
+                        long row_add) {
+  return adapter_fwd(st, M, D, z, ldz, Wd, bd, Wu, bu, scale, keep, seed, seed_dev, resid, xout,
+                     ldx, hout, row_mul, row_add);
+}
+
 static int adapter_ln_fwd(hipStream_t st, int M, int D, const void* z, long ldz, const void* Wd,
                           const float* bd, const void* Wu, const float* bu, float scale,
                           float keep, unsigned long long seed,
                           const unsigned long long* seed_dev, const void* resid, void* xout,
                           long ldx, void* hout, const float* gamma, const float* beta, void* y,
-                          long ldy, float* mean, float* rstd, int x16) {
+                          long ldy, float* mean, float* rstd, int x16, long row_mul = 1,
+                          long row_add = 0) {
   const int xb = x16 ? 2 : 4;
+  LC_CHECK_ARG(row_mul >= 1 && row_add >= 0);
   LC_CHECK_ARG(M > 0 && (D == 768 || D == 512) && ldz % 8 == 0 && ldx % (16 / xb) == 0 &&
                ldy % 8 == 0);
   // x_out / y leave as 16-B pieces through descriptors over a 16-row block (32-bit offsets)
@@ -1441,7 +1466,7 @@ static int adapter_ln_fwd(hipStream_t st, int M, int D, const void* z, long ldz,
   hipLaunchKernelGGL((adapter_ln_fwd_kernel<DD, XT>), dim3(grid), dim3(512), 0, st, M,           \
                      (const bf16_t*)z, ldz, (const bf16_t*)Wd, bd, (const bf16_t*)Wu, bu, scale,  \
                      keep, (uint64_t)seed, seed_dev, (const XT*)resid, (XT*)xout, ldx,           \
-                     (bf16_t*)hout, gamma, beta, (bf16_t*)y, ldy, mean, rstd)
+                     (bf16_t*)hout, gamma, beta, (bf16_t*)y, ldy, mean, rstd, row_mul, row_add)
   if (x16) {
     if (D == 768) LC_ALN(768, _Float16);
     else LC_ALN(512, _Float16);
@@ -1463,7 +1488,28 @@ int lc_adapter_ln_fwd(hipStream_t st, int M, int D, const void* z, long ldz, con
                         ldx, hout, gamma, beta, y, ldy, mean, rstd, 0);
 }
 
+int lc_adapter_ln_fwd_rows(hipStream_t st, int M, int D, const void* z, long ldz, const void* Wd,
+                           const float* bd, const void* Wu, const float* bu, float scale,
+                           float keep, unsigned long long seed,
+                           const unsigned long long* seed_dev, const float* resid, float* xout,
+                           long ldx, void* hout, const float* gamma, const float* beta, void* y,
+                           long ldy, float* mean, float* rstd, long row_mul, long row_add) {
+  return adapter_ln_fwd(st, M, D, z, ldz, Wd, bd, Wu, bu, scale, keep, seed, seed_dev, resid, xout,
+                        ldx, hout, gamma, beta, y, ldy, mean, rstd, 0, row_mul, row_add);
+}
+
 #ifndef LC_F16  // the image tower's half residual stream (bf16 storage build only)
+int lc_adapter_ln_fwd_rows_x16(hipStream_t st, int M, int D, const void* z, long ldz,
+                               const void* Wd, const float* bd, const void* Wu, const float* bu,
+                               float scale, float keep, unsigned long long seed,
+                               const unsigned long long* seed_dev, const void* resid, void* xout,
+                               long ldx, void* hout, const float* gamma, const float* beta,
+                               void* y, long ldy, float* mean, float* rstd, long row_mul,
+                               long row_add) {
+  return adapter_ln_fwd(st, M, D, z, ldz, Wd, bd, Wu, bu, scale, keep, seed, seed_dev, resid, xout,
+                        ldx, hout, gamma, beta, y, ldy, mean, rstd, 1, row_mul, row_add);
+}
+
 int lc_adapter_ln_fwd_x16(hipStream_t st, int M, int D, const void* z, long ldz, const void* Wd,
                           const float* bd, const void* Wu, const float* bu, float scale,
                           float keep, unsigned long long seed,

@@ -46,6 +46,8 @@ SIGNATURES = {
     "lc_eot_rows": [P, c_int, c_int, P, P],
     "lc_attn_fwd": [P, c_int, c_int, c_int, P, c_long, P, c_long, P, c_int],
     "lc_attn_bwd": [P, c_int, c_int, c_int, P, c_long, P, P, c_long, P, P, c_long, c_int],
+    "lc_attn_row_fwd": [P, c_int, c_int, c_int, P, c_long, c_int, P, c_long, P, c_int],
+    "lc_attn_row_bwd": [P, c_int, c_int, c_int, P, c_long, c_int, P, P, c_long, P, P, c_long, c_int],
     "lc_attn_bwd_fp8": [P, c_int, c_int, c_int, P, c_long, P, P, c_long, P, P, c_long, P, c_long,
                         c_int],
     "lc_train_transform": [P, c_int, c_int, c_int, c_int, P, c_int, c_int, c_int, c_int, c_int, P,
@@ -63,6 +65,11 @@ SIGNATURES = {
                        P, c_long, P],
     "lc_adapter_ln_fwd": [P, c_int, c_int, P, c_long, P, P, P, P, c_float, c_float, c_ulonglong,
                           P, P, P, c_long, P, P, P, P, c_long, P, P],
+    "lc_adapter_fwd_rows": [P, c_int, c_int, P, c_long, P, P, P, P, c_float, c_float, c_ulonglong,
+                            P, P, P, c_long, P, c_long, c_long],
+    "lc_adapter_ln_fwd_rows": [P, c_int, c_int, P, c_long, P, P, P, P, c_float, c_float,
+                               c_ulonglong, P, P, P, c_long, P, P, P, P, c_long, P, P, c_long,
+                               c_long],
     "lc_adapter_bwd": [P, c_int, c_int, P, c_long, P, P, P, c_float, c_float, P, P, c_long],
     "lc_adapter_wgrad": [P, c_int, c_int, P, c_long, P, P, c_long, P, c_float, P, P, P, P],
     "lc_adapter_wgrad_ws": [P, c_int, c_int, P, c_long, P, P, c_long, P, c_float, P, P, P, P, P,
@@ -100,7 +107,8 @@ SIGNATURES = {
 # the IEEE-half (text tower) forms: same arguments (include/lc_clip.h, "IEEE-half storage")
 F16_ENTRY_POINTS = ("lc_gemm_nt", "lc_gemm_nt_ws", "lc_gemm_tn", "lc_gemm_tn_ws",
                     "lc_layernorm_fwd", "lc_layernorm_bwd", "lc_attn_fwd", "lc_attn_bwd",
-                    "lc_attn_bwd_set_form",
+                    "lc_attn_bwd_set_form", "lc_attn_row_fwd", "lc_attn_row_bwd",
+                    "lc_adapter_fwd_rows", "lc_adapter_ln_fwd_rows",
                     "lc_cast_bf16", "lc_merge_weight", "lc_cast_weights_bf16",
                     "lc_merge_weights_bf16", "lc_lora_grad", "lc_lora_grad_ws", "lc_adapter_fwd",
                     "lc_adapter_ln_fwd", "lc_adapter_bwd", "lc_adapter_wgrad",
@@ -109,7 +117,7 @@ SIGNATURES.update({n + "_f16": SIGNATURES[n] for n in F16_ENTRY_POINTS})
 # the image tower's half residual stream (include/lc_clip.h "x16"): the f32 forms' arguments
 SIGNATURES.update({n + "_x16": SIGNATURES[n] for n in (
     "lc_layernorm_fwd", "lc_layernorm_bwd", "lc_vit_embed_ln", "lc_adapter_ln_fwd",
-    "lc_layernorm_fwd_fp8", "lc_layernorm_bwd_fp8")})
+    "lc_adapter_ln_fwd_rows", "lc_layernorm_fwd_fp8", "lc_layernorm_bwd_fp8")})
 SIGNATURES["lc_layernorm_bwd_g16"] = SIGNATURES["lc_layernorm_bwd"]
 SIGNATURES["lc_adapter_wgrad_ws_unscaled"] = SIGNATURES["lc_adapter_wgrad_ws"] + [P]
 SIGNATURES["lc_adapter_wgrad_ws_unscaled_g16"] = SIGNATURES["lc_adapter_wgrad_ws_unscaled"]

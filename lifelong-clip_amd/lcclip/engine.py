@@ -261,7 +261,7 @@ class BlockStack:
 
     # ------------------------------------------------------------------ forward
     def forward(self, x, n_seq: int, L: int, save: bool, training: bool = False, prompts=None,
-                stop=None, replace=None, first_ln1=None, last_ln=None):
+                stop=None, replace=None, first_ln1=None, last_ln=None, last_rows=False):
         """x: f32 [n_seq*L, D] residual stream, or float16 (the reference's autocast residual
         dtype, model.py:194-200 / 439-442: the fused adapter tower with last_ln, the LoRA tower,
         the frozen prompt towers of MVP / MaPLe). Returns (x_out, saved-per-layer or None).
@@ -278,7 +278,12 @@ class BlockStack:
         block's ln_1 of x already computed (ops.vit_embed_ln), used when that block runs on x
         unchanged (no prompt rows appended or replaced there, bf16 operands). last_ln: {w, b, y,
         mean, rstd} — the LayerNorm after the stack (ln_post) fused into the last block's
-        adapter (ops.adapter_ln_fwd): y bf16 [M, D] and its statistics over every row."""
+        adapter (ops.adapter_ln_fwd): y bf16 [M, D] and its statistics over every row.
+        last_rows (rows_ok()): the caller reads row 0 of every sequence of the result only (the
+        image tower's head, model.py:782), so the last block's row-wise part — out-proj, both
+        adapters, ln_2, c_fc, c_proj and last_ln — runs on those n_seq rows: its attention is
+        ops.attn_row_fwd, x_out and last_ln's y / mean / rstd are compact ([n_seq, D] / [n_seq]),
+        and the adapter dropout draws the masks rows i * L had (ops.adapter_fwd(rows=...))."""
         self.stage()
         M, D = x.shape
         xdt = x.dtype  # the residual stream's
@@ -305,6 +310,8 @@ class BlockStack:
         e_resid = EPI_RESID16 if xdt == F16 else EPI_RESID
         ln1_ready = None
         n_run = len(self.blocks) if stop is None else min(stop, len(self.blocks))
+        if last_rows and not (self.rows_ok() and not prompts and not replace and stop is None):
+            raise ValueError("last_rows: the bf16 adapter stack without prompt rows")
         carried = 0  # prompt rows x carries from the previous layer (kept: same count here)
         for idx, (blk, st) in enumerate(zip(self.blocks, self.staged)):
             if stop is not None and idx >= stop:
@@ -349,27 +356,41 @@ class BlockStack:
                     ops.layernorm_fwd(x, blk.ln_1.weight, blk.ln_1.bias, h1, mean1, rstd1)
                 self._gemm(st, "wqkv", h1, EPI_BF16, qkv, bias=blk.attn.in_proj_bias)
             ln1_ready = None
-            O = _empty((Mx, D), self.dt, dev)
-            lse = _empty((n_seq * H, Lx), F32, dev)
-            ops.attn_fwd(qkv, O, lse, n_seq, Lx, H, self.causal)
-            x_mid = _empty((Mx, D), xdt, dev)
+            # rows of the row-wise part: all of them, or (last_rows, last block) row 0 of every
+            # sequence — xr their residual input, rid their dropout row ids
+            rows = last_rows and idx == len(self.blocks) - 1
+            Mr, xr, rid = Mx, x, None
+            if rows:
+                Mr, rid = n_seq, (Lx, 0)
+                xr = _empty((Mr, D), xdt, dev)
+                xr.copy_(x.view(n_seq, Lx, D)[:, 0])
+                th = tmp_h[:Mr]
+                O = _empty((Mr, D), self.dt, dev)
+                lse = _empty((n_seq * H,), F32, dev)
+                ops.attn_row_fwd(qkv, O, lse, n_seq, Lx, H, 0, self.causal)
+            else:
+                O = _empty((Mx, D), self.dt, dev)
+                lse = _empty((n_seq * H, Lx), F32, dev)
+                ops.attn_fwd(qkv, O, lse, n_seq, Lx, H, self.causal)
+            x_mid = _empty((Mr, D), xdt, dev)
             if self.variant == "adapter":
                 ad = blk.adaptmlp
                 keep = 1.0 - ad.dropout if (training and ad.dropout > 0) else 1.0
                 seed1 = next(_seed_counter) * 0x9E3779B1
-                z1 = _empty((Mx, D), self.dt, dev)
+                z1 = _empty((Mr, D), self.dt, dev)
                 ops.gemm_nt(O, st.wo, EPI_BF16, z1, bias=blk.attn.out_proj.bias)
-                hd1 = _empty((Mx, ad.down_size), self.dt, dev)
-                mean2 = _empty((Mx,), F32, dev)
-                rstd2 = _empty((Mx,), F32, dev)
+                hd1 = _empty((Mr, ad.down_size), self.dt, dev)
+                mean2 = _empty((Mr,), F32, dev)
+                rstd2 = _empty((Mr,), F32, dev)
                 if fuse_ln and q_g is None:
                     ops.adapter_ln_fwd(z1, st.wd, ad.down_proj.bias, st.wu, ad.up_proj.bias,
-                                       ad.scale, keep, seed1, x, x_mid, hd1, blk.ln_2.weight,
-                                       blk.ln_2.bias, th, mean2, rstd2, seed_dev=self.seed_dev)
+                                       ad.scale, keep, seed1, xr, x_mid, hd1, blk.ln_2.weight,
+                                       blk.ln_2.bias, th, mean2, rstd2, seed_dev=self.seed_dev,
+                                       rows=rid)
                     ln2_done = True
                 else:
                     ops.adapter_fwd(z1, st.wd, ad.down_proj.bias, st.wu, ad.up_proj.bias, ad.scale,
-                                    keep, seed1, x, x_mid, hd1, seed_dev=self.seed_dev)
+                                    keep, seed1, xr, x_mid, hd1, seed_dev=self.seed_dev, rows=rid)
                     ln2_done = False
                 s.update(z1=z1, hd1=hd1, keep=keep)
             else:
@@ -377,7 +398,7 @@ class BlockStack:
                 mean2 = _empty((Mx,), F32, dev)
                 rstd2 = _empty((Mx,), F32, dev)
                 ln2_done = False
-            pre = _empty((Mx, 4 * D), self.dt, dev) if save else tmp_pre[:Mx]
+            pre = _empty((Mr, 4 * D), self.dt, dev) if save else tmp_pre[:Mr]
             # training saves QuickGELU'(pre) (the c_fc dX epilogue is then a plain multiply)
             if q_g is not None:
                 # ln_2 and QuickGELU(pre) only as the fp8 operands of c_fc / c_proj (inference
@@ -395,15 +416,25 @@ class BlockStack:
                 if not ln2_done:
                     ops.layernorm_fwd(x_mid, blk.ln_2.weight, blk.ln_2.bias, th, mean2, rstd2)
                 self._gemm(st, "wfc", th, EPI_GELU_D if save else EPI_GELU, pre,
-                           bias=blk.mlp.c_fc.bias, out1=tmp_g[:Mx])
-                wpr = lambda epi, out0, **kw: self._gemm(st, "wpr", tmp_g[:Mx], epi, out0, **kw)  # noqa: E731
-            x_out = _empty((Mx, D), xdt, dev)
+                           bias=blk.mlp.c_fc.bias, out1=tmp_g[:Mr])
+                wpr = lambda epi, out0, **kw: self._gemm(st, "wpr", tmp_g[:Mr], epi, out0, **kw)  # noqa: E731
+                if rows and not self.ROW_BWD:
+                    # K = 3072: the full-size launch sums the rows of its ragged last round of
+                    # tiles split over K (gemm8's split-K tail), another f32 order than a launch
+                    # at M = n_seq. c_proj runs at full size on an operand that is zero off the
+                    # live rows, so z2 keeps the full path's bits
+                    gf, zf = self._blank_rows(tmp_g, n_seq, Lx), _empty((Mx, D), self.dt, dev)
+
+                    def wpr(epi, out0, **kw):
+                        self._gemm(st, "wpr", gf, epi, zf, **kw)
+                        out0.copy_(zf.view(n_seq, Lx, D)[:, 0])
+            x_out = _empty((Mr, D), xdt, dev)
             if self.variant == "adapter":
                 ad = blk.adaptmlp
                 seed2 = next(_seed_counter) * 0x9E3779B1
-                z2 = _empty((Mx, D), self.dt, dev)
+                z2 = _empty((Mr, D), self.dt, dev)
                 wpr(EPI_BF16, z2, bias=blk.mlp.c_proj.bias)
-                hd2 = _empty((Mx, ad.down_size), self.dt, dev)
+                hd2 = _empty((Mr, ad.down_size), self.dt, dev)
                 nxt = idx + 1
                 if (fuse_ln and nxt < len(self.blocks) and (stop is None or nxt < stop)
                         and not P_of.get(nxt, 0) and not P and not (replace and nxt in replace)):
@@ -418,15 +449,17 @@ class BlockStack:
                     ln1_ready = (m1, r1)
                 elif (last_ln is not None and fuse_ln and nxt == len(self.blocks) and not P
                       and stop is None):
-                    # the LayerNorm after the stack (ln_post) over every row
+                    # the LayerNorm after the stack (ln_post) over every row (last_rows: over
+                    # the rows the block still has)
                     ops.adapter_ln_fwd(z2, st.wd, ad.down_proj.bias, st.wu, ad.up_proj.bias,
                                        ad.scale, s["keep"], seed2, x_mid, x_out, hd2,
                                        last_ln["w"], last_ln["b"], last_ln["y"], last_ln["mean"],
-                                       last_ln["rstd"], seed_dev=self.seed_dev)
+                                       last_ln["rstd"], seed_dev=self.seed_dev, rows=rid)
                     last_ln["done"] = True
                 else:
                     ops.adapter_fwd(z2, st.wd, ad.down_proj.bias, st.wu, ad.up_proj.bias, ad.scale,
-                                    s["keep"], seed2, x_mid, x_out, hd2, seed_dev=self.seed_dev)
+                                    s["keep"], seed2, x_mid, x_out, hd2, seed_dev=self.seed_dev,
+                                    rows=rid)
                 s.update(z2=z2, hd2=hd2)
             else:
                 wpr(e_resid, x_out, bias=blk.mlp.c_proj.bias, aux=x_mid)
@@ -436,7 +469,8 @@ class BlockStack:
                      and P_of.get(idx + 1, 0) == P and not (replace and idx + 1 in replace))
             if save:
                 s.update(x_in=x, mean1=mean1, rstd1=rstd1, qkv=qkv, O=O, lse=lse, x_mid=x_mid,
-                         mean2=mean2, rstd2=rstd2, gd=pre, P=P, pkeep=pkeep, inherit=inherit)
+                         mean2=mean2, rstd2=rstd2, gd=pre, P=P, pkeep=pkeep, inherit=inherit,
+                         rows=rows)
                 if replace and idx in replace:
                     s["R"] = (replace[idx][0], replace[idx][1].shape[-2])
                 if self.variant == "lora":
@@ -451,7 +485,7 @@ class BlockStack:
     # ------------------------------------------------------------------ backward
     def backward(self, saved, dx, dxb, grads, n_seq: int, L: int, on_layer=None,
                  grad_stream=None, need_dx: bool = True, prompt_grads=None,
-                 keep_input: bool = False, gscale=None):
+                 keep_input: bool = False, gscale=None, last_rows=None):
         """dx f32 / dxb bf16 [rows, D]: gradient w.r.t. the stack output. grads: dict
         param -> f32 tensor (accumulated). on_layer(li) is called once layer li's PEFT gradients
         have been launched (layers run last to first). Returns (dx, dxb) w.r.t. the stack input.
@@ -481,7 +515,14 @@ class BlockStack:
         set by the caller: ops.grad_pow2_normalize) that the weight gradients divide out. The
         adapter tower then keeps no bf16 copies (dxb may be None): its adapter backward and
         weight-gradient launches read the half gradient directly (ops.adapter_bwd / _wgrad
-        _g16 forms, bit-identical to reading the copy)."""
+        _g16 forms, bit-identical to reading the copy).
+
+        last_rows: (g, g16) [n_seq, D] — the gradient w.r.t. the compact output of a
+        forward(last_rows=True) (g16 None with a half gradient read directly). (dx, dxb) is then
+        the caller's all-zero full-size pair (RowGrad): the last block's row-wise chain runs on the
+        n_seq rows, ops.attn_row_bwd writes the full dq | dk | dv, and the chain's compact result
+        is scattered into rows i * L of dx as the residual term of that block's ln_1 backward
+        (every other row of it is zero in the full computation too)."""
         M, D = dx.shape
         gdt = dx.dtype
         if gdt != F32 and (gscale is None or prompt_grads is not None
@@ -540,13 +581,20 @@ class BlockStack:
                     v[:, L:] = 0
                 cur = e
             gx, gxb = _rows(pairs[cur][0], Mx), _rows(pairs[cur][1], Mx)
+            rows = bool(s.get("rows"))
+            if rows != (last_rows is not None and li == len(self.blocks) - 1):
+                raise ValueError("last_rows: the forward's compact last block and its gradient")
+            Mr = Mx
+            if rows:
+                Mr = n_seq
+                gx, gxb = last_rows
             out = next(i for i in range(len(pairs)) if i != cur and (
                 i != 0 or (not keep_input and (P == 0 or pairs[0][0].shape[0] >= Mx))))
             ox, oxb = _rows(pairs[out][0], Mx), _rows(pairs[out][1], Mx)
             # ---- MLP sub-block: x_out = x_mid + [A](c_proj(gelu(c_fc(ln_2(x_mid)))))
             if self.variant == "adapter":
                 dY = self._adapter_bwd(blk, st, gx if nocopy else gxb, s["hd2"], s["z2"],
-                                       s["keep"], dz[:Mx], grads)
+                                       s["keep"], dz[:Mr], grads, pad=(n_seq, Lx) if rows else None)
             else:
                 dY = gxb
             if q_da is not None:
@@ -556,27 +604,50 @@ class BlockStack:
                                     q_out=q_da.narrow(Mx))
                 ops.gemm_nt_fp8(q, st.q["wfcT"], EPI_BF16, dh[:Mx])
             else:
-                self._gemm(st, "wprT", dY, EPI_MUL, da[:Mx], aux=s["gd"])
-                self._gemm(st, "wfcT", da[:Mx], EPI_BF16, dh[:Mx])
-            ops.layernorm_bwd(dh[:Mx], s["x_mid"], s["mean2"], s["rstd2"], blk.ln_2.weight,
-                              dx_mid[:Mx], _rows(dx_midb, Mx), dres=gx)
+                self._gemm(st, "wprT", dY, EPI_MUL, da[:Mr], aux=s["gd"])
+                if rows and not self.ROW_BWD:  # (K = 3072: as c_proj in the forward)
+                    self._gemm(st, "wfcT", self._blank_rows(da, n_seq, Lx), EPI_BF16, dh[:Mx])
+                    dh[:Mr] = dh[:Mx].view(n_seq, Lx, D)[:, 0].clone()
+                else:
+                    self._gemm(st, "wfcT", da[:Mr], EPI_BF16, dh[:Mr])
+            ops.layernorm_bwd(dh[:Mr], s["x_mid"], s["mean2"], s["rstd2"], blk.ln_2.weight,
+                              dx_mid[:Mr], _rows(dx_midb, Mr), dres=gx)
             # ---- attention sub-block: x_mid = x_in + [A](out_proj(attn(ln_1(x_in))))
             first = li == 0 and not need_dx
             if self.variant == "adapter":
-                dY = self._adapter_bwd(blk, st, dx_mid[:Mx] if nocopy else dx_midb[:Mx],
-                                       s["hd1"], s["z1"], s["keep"], None if first else dz[:Mx],
-                                       grads)
+                dY = self._adapter_bwd(blk, st, dx_mid[:Mr] if nocopy else dx_midb[:Mr],
+                                       s["hd1"], s["z1"], s["keep"], None if first else dz[:Mr],
+                                       grads, pad=(n_seq, Lx) if rows else None)
             else:
                 dY = dx_midb[:Mx]
             if first and self.variant != "lora":
                 self._layer_done(li, grad_stream, on_layer)
                 break
-            ops.gemm_nt(dY, st.woT, EPI_BF16, dO[:Mx])
+            ops.gemm_nt(dY, st.woT, EPI_BF16, dO[:Mr])
             attn = blk.attn
             if self.variant == "lora":
                 self._lora_grad(dY, s["O"], attn.out_proj.lora_A, attn.out_proj.lora_B,
                                 attn.scaling, grads, st.lora_out)
-            if q_dqkv is not None and not first:
+            if rows and self.ROW_BWD:
+                qd = None
+                ops.attn_row_bwd(s["qkv"], s["O"], dO[:Mr], s["lse"], dqkv[:Mx], n_seq, Lx, H, 0,
+                                 self.causal)
+            elif rows:
+                # the full backward kernel on its full-size operands with the dead rows blank:
+                # dO and O zero off row 0 (their rows' Delta, dP and dS are then exact zeros, as
+                # with the full path's dO = 0) and lse = 1e30 there (P = 0, the kernel's own value
+                # for padded rows), so dq | dk | dv are the full path's bit for bit. da and dh are
+                # free here (the MLP chain is done, QKV dX rewrites dh below)
+                qd = None
+                dOf, Of = da.view(-1)[:Mx * D].view(Mx, D), dh[:Mx]
+                lsef = torch.full((n_seq * H, Lx), 1e30, dtype=F32, device=dev)
+                Of.zero_()
+                Of.view(n_seq, Lx, D)[:, 0] = s["O"]
+                dOf.zero_()
+                dOf.view(n_seq, Lx, D)[:, 0] = dO[:Mr]
+                lsef[:, 0] = s["lse"]
+                ops.attn_bwd(s["qkv"], Of, dOf, lsef, dqkv[:Mx], n_seq, Lx, H, self.causal)
+            elif q_dqkv is not None and not first:
                 qd = ops.attn_bwd_fp8(s["qkv"], s["O"], dO[:Mx], s["lse"], q_dqkv.narrow(Mx), n_seq,
                                       Lx, H, self.causal)
             else:
@@ -593,6 +664,12 @@ class BlockStack:
                 ops.gemm_nt_fp8(qd, st.q["wqkvT"], EPI_BF16, dh[:Mx])
             else:
                 self._gemm(st, "wqkvT", dqkv[:Mx], EPI_BF16, dh[:Mx])
+            dres1 = dx_mid[:Mx]
+            if rows:
+                # the caller's zero buffer with the chain's rows in place (never an output
+                # buffer: keep_input)
+                dres1 = pairs[0][0][:Mx]
+                dres1.view(n_seq, Lx, D)[:, 0] = dx_mid[:Mr]
             if fuse_ln_q and "R" not in s and not P:
                 if out not in q_mats:
                     q_mats[out] = ops.Fp8Mat(Mmax, D, dev)
@@ -602,7 +679,7 @@ class BlockStack:
             else:
                 q_of.pop(out, None)
                 ops.layernorm_bwd(dh[:Mx], s["x_in"], s["mean1"], s["rstd1"], blk.ln_1.weight, ox,
-                                  oxb, dres=dx_mid[:Mx])
+                                  oxb, dres=dres1)
             ev = self._layer_done(li, grad_stream, on_layer)
             if "R" in s:
                 r0, pr = s["R"]
@@ -666,7 +743,13 @@ class BlockStack:
             raise KeyError("missing gradient buffer for a trainable parameter")
         return g
 
-    def _adapter_bwd(self, blk, st, gout, h, z, keep, dz, grads):
+    def _adapter_bwd(self, blk, st, gout, h, z, keep, dz, grads, pad=None):
+        """pad = (n_seq, L): gout, h and z hold row 0 of every sequence only (the compact last
+        block). Their weight-gradient launch runs on full-size operands that are zero on every
+        other row, as the full path's gradient is: the same walkers sum the same rows in the
+        same order, so these f32 gradients are the full path's bit for bit (a launch at M = n_seq
+        sums them in another order, and AdamW's first steps turn even that 3e-8 into flipped
+        16-bit weights within a few updates). Fills and launch are on the side stream."""
         ad = blk.adaptmlp
         M = gout.shape[0]
         dpre = _empty((M, ad.down_size), self.dt, gout.device)
@@ -674,6 +757,12 @@ class BlockStack:
         with self._side():
             if getattr(self, "_gs", None) is not None:
                 dpre.record_stream(self._gs)
+            if pad is not None and not self.ROW_BWD:
+                def full(t):
+                    f = torch.zeros((pad[0] * pad[1], t.shape[1]), dtype=t.dtype, device=t.device)
+                    f.view(pad[0], pad[1], -1)[:, 0] = t
+                    return f
+                gout, h, z, dpre = full(gout), full(h), full(z), full(dpre)
             ops.adapter_wgrad(gout, h, z, dpre, ad.scale, self._grad(grads, ad.up_proj.weight),
                               self._grad(grads, ad.up_proj.bias),
                               self._grad(grads, ad.down_proj.weight),
@@ -684,6 +773,28 @@ class BlockStack:
     # LCCLIP_HALF_GRAD_DIRECT=0: the adapter tower's half residual gradient with bf16 copies for
     # its adapter backward launches, as before lc_adapter_*_g16 (A/B experiments)
     HALF_GRAD_DIRECT = os.environ.get("LCCLIP_HALF_GRAD_DIRECT", "1") != "0"
+
+    # LCCLIP_ROW_BWD=1: the compact last block's attention backward on ops.attn_row_bwd (reads K
+    # and V only) and its weight gradients at M = n_seq: faster, and equal to the default up to
+    # f32 summation order. One flipped 16-bit rounding there moves the lower layers' gradients
+    # by ~1e-3 of their norm, so the default keeps the full kernels on blanked full-size
+    # operands and with them the full path's bits. A/B experiments
+    ROW_BWD = os.environ.get("LCCLIP_ROW_BWD", "0") == "1"
+
+    @staticmethod
+    def _blank_rows(buf, n_seq, L):
+        """buf [>= n_seq*L, W] whose first n_seq rows are the compact rows: the same buffer as
+        [n_seq*L, W] with them at rows i * L and zeros everywhere else."""
+        c = buf[:n_seq].clone()
+        f = buf[:n_seq * L]
+        f.zero_()
+        f.view(n_seq, L, -1)[:, 0] = c
+        return f
+
+    def rows_ok(self):
+        """forward(last_rows=True) applies: the adapter stack on bf16 / IEEE-half GEMMs (LoRA,
+        the frozen prompt towers and fp8 keep every row)."""
+        return self.variant == "adapter" and self.precision == "bf16"
 
     def half_grad_direct(self):
         """A half residual gradient's consumers read it directly (no bf16 copies): the adapter
@@ -977,6 +1088,10 @@ class ImageTower:
     # LCCLIP_HALF_GRAD=0: a half residual stream with an f32 gradient (A/B experiments)
     HALF_GRAD = os.environ.get("LCCLIP_HALF_GRAD", "1") != "0"
 
+    # the last block's row-wise part on the CLS rows only (its other output rows are read by
+    # nothing, model.py:782, and their gradient is zero). LCCLIP_LAST_ROWS=0: every row (A/Bs)
+    LAST_ROWS = os.environ.get("LCCLIP_LAST_ROWS", "1") != "0"
+
     def _resid16(self):
         st = self.stack
         if not (self.RESID16 and self.visual.width in (512, 768)) or st.dt != BF16:
@@ -1013,15 +1128,24 @@ class ImageTower:
         """forward() from a precomputed embed() (the MVP query and prompt passes share x0)."""
         self._stage()
         last = None
+        rows = self.LAST_ROWS and self.stack.rows_ok() and not prompts and not replace
         if x0.dtype == F16 and self.stack.variant == "adapter":
-            # ln_post fused into the last block's adapter over every row
+            # ln_post fused into the last block's adapter over every row (rows: the CLS rows)
             v = self.visual
             M, D = x0.shape
+            if rows:
+                M = n
             last = dict(w=v.ln_post.weight, b=v.ln_post.bias, y=_empty((M, D), BF16, x0.device),
                         mean=_empty((M,), F32, x0.device), rstd=_empty((M,), F32, x0.device))
         x, saved = self.stack.forward(x0, n, L, save, training, prompts=prompts, replace=replace,
-                                      first_ln1=first_ln1, last_ln=last)
-        if last is not None and last.get("done"):
+                                      first_ln1=first_ln1, last_ln=last, last_rows=rows)
+        if rows:  # x [n, D]: the CLS rows
+            cls_idx = torch.arange(n, device=x.device, dtype=torch.int32) * L
+            if last is not None and last.get("done"):
+                lnp, mean, rstd = last["y"], last["mean"], last["rstd"]
+            else:
+                lnp, _, mean, rstd = self._ln_post(x, n, 1, self.stack.dt)
+        elif last is not None and last.get("done"):
             cls_idx = torch.arange(n, device=x.device, dtype=torch.int32) * L
             ci = cls_idx.long()
             lnp, mean, rstd = last["y"][ci], last["mean"][ci], last["rstd"][ci]
@@ -1029,7 +1153,7 @@ class ImageTower:
             lnp, cls_idx, mean, rstd = self._ln_post(x, n, L, self.stack.dt)
         f = _empty((n, self.projT.shape[0]), F32, x.device)
         ops.gemm_nt(lnp, self.projT, EPI_F32, f)
-        ctx = dict(saved=saved, x=x, cls_idx=cls_idx, mean=mean, rstd=rstd, n=n, L=L,
+        ctx = dict(saved=saved, x=x, cls_idx=cls_idx, mean=mean, rstd=rstd, n=n, L=L, rows=rows,
                    prompt_layers=sorted(int(k) for k in (prompts or {}))) if save else None
         return f, ctx
 
@@ -1072,12 +1196,22 @@ class ImageTower:
                                     dt=dt, gdt=F16 if half else F32)
         if half and self.stack.half_grad_direct():
             dxb = None  # the adapter backward reads the half gradient itself (no bf16 copy)
-        ops.layernorm_bwd(dln, ctx["x"], ctx["mean"], ctx["rstd"], v.ln_post.weight, dx, dxb,
-                          row_idx=ctx["cls_idx"])
+        last_rows = None
+        if ctx.get("rows"):
+            # ctx["x"] holds the CLS rows only: ln_post's backward on them; (dx, dxb) stays zero
+            # until the last block scatters its result into the CLS rows
+            gc = _empty((n, D), dx.dtype, dev)
+            gcb = None if dxb is None else _empty((n, D), dt, dev)
+            ops.layernorm_bwd(dln, ctx["x"], ctx["mean"], ctx["rstd"], v.ln_post.weight, gc, gcb)
+            last_rows = (gc, gcb)
+        else:
+            ops.layernorm_bwd(dln, ctx["x"], ctx["mean"], ctx["rstd"], v.ln_post.weight, dx, dxb,
+                              row_idx=ctx["cls_idx"])
         # the input (patch embedding) is frozen; prompts appended at layer 0 need its backward
         gx, _ = self.stack.backward(ctx["saved"], dx, dxb, grads, n, L, on_layer, grad_stream,
                                     need_dx=need_dx or 0 in ctx["prompt_layers"],
-                                    prompt_grads=prompt_grads, keep_input=True, gscale=gsc)
+                                    prompt_grads=prompt_grads, keep_input=True, gscale=gsc,
+                                    last_rows=last_rows)
         if sg is not None:
             sg.add_to(out_grads)
             if out_pg is not None:

@@ -342,6 +342,37 @@ def attn_bwd(qkv, O, dO, lse, dqkv, n_seq, L, H, causal):
     return dqkv
 
 
+def attn_row_fwd(qkv, O_row, lse_row, n_seq, L, H, row, causal):
+    """Query row `row` of every sequence: O_row [n_seq, H*64] and lse_row [n_seq*H] are that row
+    of attn_fwd's O and lse (lc_attn_row_fwd)."""
+    if O_row.dtype != qkv.dtype or qkv.dtype not in HALF:
+        raise TypeError("attn_row_fwd: qkv and O_row must share the 16-bit type")
+    if tuple(O_row.shape) != (n_seq, H * 64) or O_row.stride(1) != 1 or lse_row.numel() != n_seq * H \
+            or lse_row.dtype != F32 or not lse_row.is_contiguous() or qkv.shape[0] != n_seq * L:
+        raise ValueError("attn_row_fwd: O_row [n_seq, H*64], lse_row f32 [n_seq*H], qkv [n_seq*L, .]")
+    call(_sym16("lc_attn_row_fwd", qkv, O_row), stream_of(qkv), n_seq, L, H, ptr(qkv), qkv.stride(0),
+         int(row), ptr(O_row), O_row.stride(0), ptr(lse_row), int(causal))
+    return O_row
+
+
+def attn_row_bwd(qkv, O_row, dO_row, lse_row, dqkv, n_seq, L, H, row, causal):
+    """attn_bwd with dO zero off row `row` of every sequence, from the compact O_row / dO_row /
+    lse_row: all n_seq*L rows of dqkv are written (lc_attn_row_bwd)."""
+    if O_row.stride(0) != dO_row.stride(0):
+        raise ValueError("O_row and dO_row must share a row stride")
+    if len({t.dtype for t in (qkv, O_row, dO_row, dqkv)}) != 1 or qkv.dtype not in HALF:
+        raise TypeError("attn_row_bwd: qkv, O_row, dO_row and dqkv must share the 16-bit type")
+    if tuple(O_row.shape) != (n_seq, H * 64) or tuple(dO_row.shape) != (n_seq, H * 64) \
+            or O_row.stride(1) != 1 or dO_row.stride(1) != 1 or lse_row.numel() != n_seq * H \
+            or lse_row.dtype != F32 or not lse_row.is_contiguous() \
+            or qkv.shape[0] != n_seq * L or tuple(dqkv.shape) != (n_seq * L, 3 * H * 64):
+        raise ValueError("attn_row_bwd: shape mismatch")
+    call(_sym16("lc_attn_row_bwd", qkv, O_row, dO_row, dqkv), stream_of(qkv), n_seq, L, H, ptr(qkv),
+         qkv.stride(0), int(row), ptr(O_row), ptr(dO_row), O_row.stride(0), ptr(lse_row), ptr(dqkv),
+         dqkv.stride(0), int(causal))
+    return dqkv
+
+
 def attn_bwd_fp8(qkv, O, dO, lse, q, n_seq, L, H, causal):
     """attn_bwd with dq|dk|dv written straight into q, an Fp8Mat [n_seq*L, 3*H*64] (the fp8
     QKV input-gradient GEMM's A operand; the codes of attn_bwd + quant_fp8). L <= 224."""
@@ -469,24 +500,36 @@ def lora_grad_1p(dY, X, a_pad, bt_pad, r, scaling, dA, dB, gscale=None):
          ptr(dB), ptr(ws), ws.numel(), *extra)
 
 
-def adapter_fwd(z, Wd, bd, Wu, bu, scale, keep, seed, resid, xout, h, seed_dev=None):
+def _row_ids(rows):
+    """(mul, add) of the dropout row id m * mul + add of the _rows entry points."""
+    mul, add = (int(v) for v in rows)
+    if mul < 1 or add < 0:
+        raise ValueError("rows: (mul >= 1, add >= 0)")
+    return mul, add
+
+
+def adapter_fwd(z, Wd, bd, Wu, bu, scale, keep, seed, resid, xout, h, seed_dev=None, rows=None):
     """xout = resid + z + scale * up(drop(relu(down(z)))): resid / xout f32 [M, D] (the kernel
-    reads and writes them raw; a half residual stream goes through adapter_ln_fwd)."""
+    reads and writes them raw; a half residual stream goes through adapter_ln_fwd).
+    rows: (mul, add) — row m draws the dropout mask of row m * mul + add (rows gathered from a
+    larger launch keep the mask they had there; lc_adapter_fwd_rows)."""
     M, D = z.shape
     if resid.dtype != F32 or xout.dtype != F32:
         raise TypeError("adapter_fwd: resid and xout must be f32")
     if tuple(resid.shape) != (M, D) or tuple(xout.shape) != (M, D) or resid.stride() != xout.stride() \
             or xout.stride(1) != 1:
         raise ValueError("adapter_fwd: resid and xout must be row-major [M, D] views of one stride")
-    call(_sym16("lc_adapter_fwd", z, Wd, Wu, h), stream_of(z), M, D, ptr(z), z.stride(0), ptr(Wd), ptr(bd), ptr(Wu),
+    name = "lc_adapter_fwd" if rows is None else "lc_adapter_fwd_rows"
+    call(_sym16(name, z, Wd, Wu, h), stream_of(z), M, D, ptr(z), z.stride(0), ptr(Wd), ptr(bd), ptr(Wu),
          ptr(bu), float(scale), float(keep), int(seed) & 0xFFFFFFFFFFFFFFFF, ptr(seed_dev),
-         ptr(resid), ptr(xout), xout.stride(0), ptr(h))
+         ptr(resid), ptr(xout), xout.stride(0), ptr(h), *(() if rows is None else _row_ids(rows)))
 
 
 def adapter_ln_fwd(z, Wd, bd, Wu, bu, scale, keep, seed, resid, xout, h, gamma, beta, y, mean,
-                   rstd, seed_dev=None):
+                   rstd, seed_dev=None, rows=None):
     """adapter_fwd, then y = LayerNorm(xout) (bf16, statistics saved) in one launch. resid /
-    xout: f32, or float16 (the image tower's half residual stream; xout row stride % 8 == 0)."""
+    xout: f32, or float16 (the image tower's half residual stream; xout row stride % 8 == 0).
+    rows: as adapter_fwd (lc_adapter_ln_fwd_rows)."""
     M, D = z.shape
     if y.dtype != z.dtype or tuple(y.shape) != (M, D) or y.stride(1) != 1:
         raise ValueError("adapter_ln_fwd: y must be a [M, D] row-major view of z's 16-bit type")
@@ -495,10 +538,11 @@ def adapter_ln_fwd(z, Wd, bd, Wu, bu, scale, keep, seed, resid, xout, h, gamma, 
         raise ValueError("adapter_ln_fwd: resid and xout must be [M, D] views of one dtype and stride")
     if xout.dtype == F16 and (xout.stride(0) % 8 or xout.data_ptr() % 16 or resid.data_ptr() % 16):
         raise ValueError("adapter_ln_fwd: half xout / resid rows must be 16-B aligned pieces")
-    call(_x16("lc_adapter_ln_fwd", xout, z, Wd, Wu, h, y), stream_of(z), M, D, ptr(z), z.stride(0), ptr(Wd), ptr(bd), ptr(Wu),
+    name = "lc_adapter_ln_fwd" if rows is None else "lc_adapter_ln_fwd_rows"
+    call(_x16(name, xout, z, Wd, Wu, h, y), stream_of(z), M, D, ptr(z), z.stride(0), ptr(Wd), ptr(bd), ptr(Wu),
          ptr(bu), float(scale), float(keep), int(seed) & 0xFFFFFFFFFFFFFFFF, ptr(seed_dev),
          ptr(resid), ptr(xout), xout.stride(0), ptr(h), ptr(gamma), ptr(beta), ptr(y),
-         y.stride(0), ptr(mean), ptr(rstd))
+         y.stride(0), ptr(mean), ptr(rstd), *(() if rows is None else _row_ids(rows)))
 
 
 def _g16(name, gout, *ts):
