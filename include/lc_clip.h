@@ -28,6 +28,9 @@ extern "C" {
 #define LC_OK 0
 #define LC_EINVAL (-1)
 #define LC_ELAUNCH (-2)
+/* a well-formed call outside what the entry point covers; nothing is launched or written, the
+ * caller takes its other path (lc_gemm_nt_rows, lc_gemm_split_plan only) */
+#define LC_EUNSUPPORTED (-3)
 
 /* GEMM epilogues for lc_gemm_nt */
 #define LC_EPI_BF16 0     /* out0 bf16 = alpha*acc + bias                                    */
@@ -69,6 +72,30 @@ int lc_gemm_nt(hipStream_t stream, int epi, int M, int N, int K, const void* A, 
 int lc_gemm_nt_ws(hipStream_t stream, int epi, int M, int N, int K, const void* A, long lda,
                   const void* B, long ldb, const float* bias, float alpha, void* out0, long ldo0,
                   void* out1, long ldo1, const void* aux, long ldaux, void* ws, long ws_bytes);
+
+/* A few rows of a large launch: out[i][:] (i < n) gets, bit for bit, what
+ * lc_gemm_nt_ws(epi, M_full, N, K, ..., ws, ws_bytes) writes to row i * mul + add when its A is
+ * zero on every other row — from the compact A [n, K] alone. The full launch sums a row of its
+ * split-K tail tiles slice by slice, another f32 order than a launch at n rows; this form takes
+ * the full launch's own plan and raster, runs the launch at n rows, computes the S slice partials
+ * of the compact rows (f32, in ws after the tickets, which stay untouched) and rewrites the rows
+ * of the tail tiles as their slice-order sum through the epilogue.
+ * Covers LC_EPI_BF16 (with or without bias) and LC_EPI_F32 at alpha = 1, for full launches on
+ * the 256x256 kernel's default schedule or on a kernel family without a split. Returns
+ * LC_EUNSUPPORTED, launching nothing, otherwise: another epilogue or alpha, a forced tile
+ * (lc_gemm_set_tile), a stream-K mode (lc_gemm_set_streamk), the hipBLASLt shape, or a
+ * workspace too small for S x n x N floats after the tickets. Pass the ws the full launch
+ * would get (its plan depends on it). out 16-B aligned, ldo % 8 == 0, mul >= 1, add >= 0,
+ * (n - 1) * mul + add < M_full.
+ * Replaces: nothing in the reference (the compact last block of the image tower keeping the
+ * full-size step's bits). */
+int lc_gemm_nt_rows(hipStream_t stream, int epi, int n, int N, int K, const void* A, long lda,
+                    const void* B, long ldb, const float* bias, float alpha, void* out, long ldo,
+                    int M_full, long mul, long add, void* ws, long ws_bytes);
+/* The split-K plan the 256x256 kernel's launch at (M, N, K) with a workspace of ws_bytes has:
+ * tiles [0, dp_tiles) whole, the rest cut into `splits` slices (1: none; also for shapes that
+ * run on a kernel family without a split). LC_EUNSUPPORTED as lc_gemm_nt_rows (tests). */
+int lc_gemm_split_plan(int M, int N, int K, long ws_bytes, int* dp_tiles, int* splits);
 
 /* Block-scaled fp8 GEMM (MX-style e4m3 operands, E8M0 scale per 32 k; fp8 MFMA
  * v_mfma_scale_f32_16x16x128_f8f6f4 at twice the bf16 rate): out = epilogue(alpha * A @ B^T + bias)
@@ -299,6 +326,17 @@ int lc_attn_row_fwd_f16(hipStream_t stream, int n_seq, int L, int H, const void*
 int lc_attn_row_bwd_f16(hipStream_t stream, int n_seq, int L, int H, const void* qkv, long ldq,
                         int row, const void* O_row, const void* dO_row, long ldo,
                         const float* lse_row, void* dqkv, long lddq, int causal);
+/* lc_attn_row_bwd's operands on the MFMA backward kernel in its single-row mode: dqkv is what
+ * lc_attn_bwd (default form) writes on full-size operands blanked off `row` — O and dO zero,
+ * lse = 1e30 there — equal element for element (a +0 may stand for a -0); lc_attn_row_bwd's VALU
+ * kernel sums in another order. The live row's query chunk alone runs phase 1, its wave alone
+ * phase 2. LC_EUNSUPPORTED when lc_attn_bwd_set_form selects a form other than the default's. */
+int lc_attn_bwd_live_row(hipStream_t stream, int n_seq, int L, int H, const void* qkv, long ldq,
+                         int row, const void* O_row, const void* dO_row, long ldo,
+                         const float* lse_row, void* dqkv, long lddq, int causal);
+int lc_attn_bwd_live_row_f16(hipStream_t stream, int n_seq, int L, int H, const void* qkv,
+                             long ldq, int row, const void* O_row, const void* dO_row, long ldo,
+                             const float* lse_row, void* dqkv, long lddq, int causal);
 /* The backward with dq|dk|dv written as the A operand of the fp8 QKV input-gradient GEMM
  * (lc_gemm_nt_fp8): e4m3 codes dqkv [n_seq*L, lddq BYTES] (lddq % 16 == 0, 16-B aligned) + E8M0
  * scales q_scale [3*H*64/128][q_rows][4] (q_rows = n_seq*L rounded up to 256), bit-identical to
@@ -566,6 +604,9 @@ int lc_gemm_nt_f16(hipStream_t stream, int epi, int M, int N, int K, const void*
 int lc_gemm_nt_ws_f16(hipStream_t stream, int epi, int M, int N, int K, const void* A, long lda,
                       const void* B, long ldb, const float* bias, float alpha, void* out0, long ldo0,
                       void* out1, long ldo1, const void* aux, long ldaux, void* ws, long ws_bytes);
+int lc_gemm_nt_rows_f16(hipStream_t stream, int epi, int n, int N, int K, const void* A, long lda,
+                        const void* B, long ldb, const float* bias, float alpha, void* out,
+                        long ldo, int M_full, long mul, long add, void* ws, long ws_bytes);
 int lc_gemm_tn_f16(hipStream_t stream, int M, int N1, int N2, const void* A, long lda, const void* B,
                    long ldb, float alpha, float* C, long ldc, float* colsum, float colsum_scale);
 int lc_gemm_tn_ws_f16(hipStream_t stream, int M, int N1, int N2, const void* A, long lda,

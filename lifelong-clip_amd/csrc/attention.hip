@@ -26,6 +26,7 @@
 //     S^T, dP^T from K / V in LDS and accumulates dQ^T = K^T dS^T; it walks the heads in reverse
 //     order so its reads hit what the key-major kernel left in L2 / the Infinity Cache.
 #include "lc_common.h"
+#include <type_traits>
 
 namespace {
 
@@ -481,15 +482,48 @@ struct BwdLds {
 // Q8: dQ / dK / dV written as the A operand of the fp8 QKV input-gradient GEMM (MaPLe's fp8
 // mode): e4m3 codes (lddq in bytes) + E8M0 scales (q_scale, q_rows), the arithmetic of
 // quant_fp8_kernel on the bf16-rounded values, so the codes equal bf16 output + quant_fp8.
-template <int NQB, bool PERSIST = (NQB >= 5), bool Q8 = false>
+//
+// ROW: one live query row per sequence (the image tower's compact last block), the result of the
+// full kernel on operands blanked off that row — O and dO zero, lse = 1e30 there — from compact
+// O / dO [n_seq, ldo] and lse [n_items]; q_rows carries the row index. On such operands every
+// query chunk but the live row's adds exact zeros to dK / dV, and every wave's dQ but its owner's
+// is zero, so phase 1 runs that chunk alone (its other 31 rows zero in LDS, -lse = -1e30) and
+// phase 2 runs on one wave; the others store zero dQ rows. Equal to the full launch up to the
+// sign of a zero. LDS holds one chunk of Q / dO / dS^T (BwdLdsRow), so NQB = 8 fits too; there
+// the full path is the key-major + query-major pair, whose dQ sums a 32-key block with key
+// 16kk + 4g + r in k-slot (g, 4kk + r): phase 2 reads its rows in that order for NQB = 8. That
+// pair also sums D = rowsum(dO * O) in two orders (key-major: 8 chunks of 8 columns, pairwise;
+// query-major: chunks g and 4 + g in sequence per lane group, then pairwise), so for NQB = 8 the
+// dS^T parked for phase 2 comes from a second dP started at the query-major -D.
+template <int NQB>
+struct BwdLdsRow {
+  static constexpr int LP = 32 * NQB;
+  static constexpr int DST_STRIDE = 32 * 2 + 16;  // BwdLds<1>'s: one chunk of queries per key row
+  static constexpr int Q_OFF = 0;                 // the Q and dO chunks lie inside the K image
+  static constexpr int DO_OFF = 32 * 128;
+  static constexpr int DST_OFF = LP * 128 > 2 * 32 * 128 ? LP * 128 : 2 * 32 * 128;
+  static constexpr int NLSE_OFF = DST_OFF + LP * DST_STRIDE;
+  static constexpr int ND_OFF = NLSE_OFF + 32 * 4;
+  static constexpr int NDQ_OFF = ND_OFF + 32 * 4;  // NQB = 8: -D in the query-major kernel's order
+  static constexpr int BYTES = NDQ_OFF + 32 * 4;
+};
+
+template <int NQB, bool PERSIST = (NQB >= 5), bool Q8 = false, bool ROW = false>
 __global__ void __launch_bounds__(64 * NQB)
 attn_bwd_kernel(int n_items, int L, int H, int D, const bf16_t* __restrict__ qkv, long ldq,
                    const bf16_t* __restrict__ O, const bf16_t* __restrict__ dO, long ldo,
                    const float* __restrict__ lse, bf16_t* __restrict__ dqkv, long lddq, int causal,
                    float scale, uint8_t* __restrict__ q_scale = nullptr, long q_rows = 0) {
+  static_assert(!(ROW && Q8), "the single-row mode writes 16-bit gradients");
   constexpr int LP = 32 * NQB;
   constexpr int NTH = 64 * NQB;
-  using Lay = BwdLds<NQB>;
+  using Lay = typename std::conditional<ROW, BwdLdsRow<NQB>, BwdLds<NQB>>::type;
+  // ROW: the live row, its chunk, and phase 2's rows of a 32-key block per k-slot half
+  const int row = ROW ? (int)q_rows : 0;
+  const int rowc = row >> 5;
+  constexpr bool KSLOT8 = ROW && NQB == 8;
+  constexpr int R_MUL = KSLOT8 ? 4 : 8, R_STEP = KSLOT8 ? 16 : 4;
+  constexpr int OOR = 0x7ffffff0;  // a buffer offset past every descriptor: the load reads zero
   __shared__ __attribute__((aligned(16))) char smem[Lay::BYTES];
   char* Qs = smem + Lay::Q_OFF;
   char* dOs = smem + Lay::DO_OFF;
@@ -505,7 +539,8 @@ attn_bwd_kernel(int n_items, int L, int H, int D, const bf16_t* __restrict__ qkv
 
   // staging: 16-B chunks of Q, dO and O rows (8 lanes per row); D = rowsum(dO*O) from the same
   // chunks (xor-shuffles) when they are written to LDS
-  constexpr int IT = LP * 8 / NTH;  // = 4
+  // (ROW: the 32 x 8 chunks of the live query chunk, over the first 256 threads' slots)
+  constexpr int IT = ROW ? (256 + NTH - 1) / NTH : LP * 8 / NTH;  // full: = 4
   uint4 qv[IT], dv[IT], ov[IT];
   float lv[IT];
   // Every global access of an item goes through a raw-buffer descriptor over that sequence's L
@@ -535,12 +570,31 @@ attn_bwd_kernel(int n_items, int L, int H, int D, const bf16_t* __restrict__ qkv
     asm volatile("" : "+v"(v));
     return v;
   };
+  // ROW: a descriptor over `bytes` bytes at p + off (one compact row, one lse value), and
+  // whether slot (thread + i * NTH) of the live chunk's image is a chunk of the live row
+  auto span_rsrc = [&](const void* p, long off, int bytes, bool ok) {
+    const uint64_t a = (uint64_t)(static_cast<const char*>(p) + (ok ? off : 0));
+    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)a);
+    const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)(a >> 32));
+    const int n = __builtin_amdgcn_readfirstlane(ok ? bytes : 0);
+    return __builtin_amdgcn_make_buffer_rsrc((void*)(((uint64_t)hi << 32) | lo), 0, n, 0x00020000);
+  };
+  auto live_slot = [&](int slot) { return slot < 256 && rowc * 32 + (slot >> 3) == row; };
   auto load_rows = [&](int it_) {
     const int tv = lane_tid();
     const bool ok = it_ < n_items;
     const auto rq = rows_rsrc(qkv, (long)(it_ / H) * L, ldq * 2, ok);
-    const auto rl = rows_rsrc(lse, (long)it_ * L, 4, ok);  // this item's L lse values
     const int cb = ((it_ % H) * 64 + (tv & 7) * 8) * 2;
+    if constexpr (ROW) {
+      const auto rl = span_rsrc(lse, (long)it_ * 4, 4, ok);  // this item's one lse value
+#pragma unroll
+      for (int i = 0; i < IT; ++i) {  // the live row's chunks; every other slot reads zero
+        const bool live = live_slot(tv + i * NTH);
+        qv[i] = bld16(rq, live ? row * (int)ldq * 2 + cb : OOR);
+        lv[i] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rl, live ? 0 : OOR, 0, 0));
+      }
+    } else {
+    const auto rl = rows_rsrc(lse, (long)it_ * L, 4, ok);  // this item's L lse values
 #pragma unroll
     for (int i = 0; i < IT; ++i) {
       const int r = (tv + i * NTH) >> 3;
@@ -548,18 +602,30 @@ attn_bwd_kernel(int n_items, int L, int H, int D, const bf16_t* __restrict__ qkv
       // rows >= L read 0 here; the padded-row value (1e30) is substituted where lv is used
       lv[i] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rl, r * 4, 0, 0));
     }
+    }
   };
   auto load_o = [&](int it_) {
     const int tv = lane_tid();
     const bool ok = it_ < n_items;
+    const int cb = ((it_ % H) * 64 + (tv & 7) * 8) * 2;
+    if constexpr (ROW) {
+      const auto rd = span_rsrc(dO, (long)(it_ / H) * ldo * 2, D * 2, ok);  // the compact row
+      const auto ro = span_rsrc(O, (long)(it_ / H) * ldo * 2, D * 2, ok);
+#pragma unroll
+      for (int i = 0; i < IT; ++i) {
+        const bool live = live_slot(tv + i * NTH);
+        dv[i] = bld16(rd, live ? cb : OOR);
+        ov[i] = bld16(ro, live ? cb : OOR);
+      }
+    } else {
     const auto rd = rows_rsrc(dO, (long)(it_ / H) * L, ldo * 2, ok);
     const auto ro = rows_rsrc(O, (long)(it_ / H) * L, ldo * 2, ok);
-    const int cb = ((it_ % H) * 64 + (tv & 7) * 8) * 2;
 #pragma unroll
     for (int i = 0; i < IT; ++i) {
       const int r = (tv + i * NTH) >> 3;
       dv[i] = bld16(rd, r * (int)ldo * 2 + cb);
       ov[i] = bld16(ro, r * (int)ldo * 2 + cb);
+    }
     }
   };
   // own key block: K / V rows kb + kt2*16 + t, as B-operand fragments
@@ -670,10 +736,12 @@ attn_bwd_kernel(int n_items, int L, int H, int D, const bf16_t* __restrict__ qkv
   const int tvh = lane_tid();  // LDS addresses recomputed per item (hoisted, they spilled)
 #pragma unroll
   for (int i = 0; i < IT; ++i) {
-    const int r = (tvh + i * NTH) >> 3;
+    const int r = (tvh + i * NTH) >> 3;  // (ROW: row r of the live chunk, slots past it idle)
     const int ch = tvh & 7;
-    *reinterpret_cast<uint4*>(Qs + r * 128 + swz(r, ch) * 16) = qv[i];
-    *reinterpret_cast<uint4*>(dOs + r * 128 + swz(r, ch) * 16) = dv[i];
+    if (!ROW || tvh + i * NTH < 256) {
+      *reinterpret_cast<uint4*>(Qs + r * 128 + swz(r, ch) * 16) = qv[i];
+      *reinterpret_cast<uint4*>(dOs + r * 128 + swz(r, ch) * 16) = dv[i];
+    }
     const uint32_t aa[4] = {ov[i].x, ov[i].y, ov[i].z, ov[i].w};
     const uint32_t bb[4] = {dv[i].x, dv[i].y, dv[i].z, dv[i].w};
     float dsum = 0.f;
@@ -683,7 +751,28 @@ attn_bwd_kernel(int n_items, int L, int H, int D, const bf16_t* __restrict__ qkv
     dsum += __shfl_xor(dsum, 1);
     dsum += __shfl_xor(dsum, 2);
     dsum += __shfl_xor(dsum, 4);
-    if (ch == 0) {
+    if constexpr (KSLOT8) {
+      // attn_bwd_q_kernel's D: lane group g adds the column pairs of chunk g, then of chunk
+      // 4 + g, in sequence; the groups meet as (g, g ^ 1), then (g, g ^ 2)
+      float tk[4], pq = 0.f;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        tk[k] = bf2f(aa[k] & 0xffff) * bf2f(bb[k] & 0xffff) + bf2f(aa[k] >> 16) * bf2f(bb[k] >> 16);
+        pq += tk[k];
+      }
+#pragma unroll
+      for (int k = 0; k < 4; ++k) pq += __shfl_xor(tk[k], 4);  // (meaningful on chunks 0..3)
+      pq += __shfl_xor(pq, 1);
+      pq += __shfl_xor(pq, 2);
+      if (ch == 0 && tvh + i * NTH < 256)
+        reinterpret_cast<float*>(smem + Lay::NDQ_OFF)[r] = -pq;
+    }
+    if constexpr (ROW) {
+      if (ch == 0 && tvh + i * NTH < 256) {
+        nd_s[r] = -dsum;
+        nlse_s[r] = live_slot(tvh + i * NTH) ? -lv[i] : -1e30f;
+      }
+    } else if (ch == 0) {
       nd_s[r] = -dsum;
       nlse_s[r] = r < L ? -lv[i] : -1e30f;
     }
@@ -706,19 +795,23 @@ attn_bwd_kernel(int n_items, int L, int H, int D, const bf16_t* __restrict__ qkv
 
   // causal: queries before the block's first key see none of its keys
   const int qc0 = causal ? w : 0;
+  // (ROW: the live row's chunk alone — the other chunks' products are exact zeros)
+  const int qc_lo = ROW ? max(qc0, rowc) : qc0, qc_hi = ROW ? rowc + 1 : NQB;
 #pragma unroll 1
-  for (int qc = qc0; qc < NQB; ++qc) {
+  for (int qc = qc_lo; qc < qc_hi; ++qc) {
     const bool edge = (kb + 32 > L) || (causal && kb + 31 > qc * 32);
+    const int lq = ROW ? 0 : qc * 32;  // the chunk's first row in the LDS images
     // B operands (k = 32 queries of this chunk): slot j<4 -> q = 4g+j, j>=4 -> 16+4g+(j-4);
     // one 16-query tile of S / dP is live at a time and packed to bf16 straight away.
     u32x4 pw[2], sw[2];
 #pragma unroll
     for (int qt = 0; qt < 2; ++qt) {
       const int q0 = qc * 32 + qt * 16 + 4 * g;
-      const f32x4 nl = *reinterpret_cast<const f32x4*>(nlse_s + q0);
-      const f32x4 nd = *reinterpret_cast<const f32x4*>(nd_s + q0);
-      const char* qrow = Qs + (qc * 32 + qt * 16) * 128;
-      const char* drow = dOs + (qc * 32 + qt * 16) * 128;
+      const int lq0 = lq + qt * 16 + 4 * g;
+      const f32x4 nl = *reinterpret_cast<const f32x4*>(nlse_s + lq0);
+      const f32x4 nd = *reinterpret_cast<const f32x4*>(nd_s + lq0);
+      const char* qrow = Qs + (lq + qt * 16) * 128;
+      const char* drow = dOs + (lq + qt * 16) * 128;
       const bf16x8 qa0 = lds16(qrow + ro0), qa1 = lds16(qrow + ro1);
       const bf16x8 da0 = lds16(drow + ro0), da1 = lds16(drow + ro1);
       f32x4 S[2], dP[2];
@@ -728,6 +821,16 @@ attn_bwd_kernel(int n_items, int L, int H, int D, const bf16_t* __restrict__ qkv
         S[k2] = mfma16(qa1, kf[k2][1], S[k2]);
         dP[k2] = mfma16(da0, vf[k2][0], nd);  // dP - D
         dP[k2] = mfma16(da1, vf[k2][1], dP[k2]);
+      }
+      f32x4 dPq[2];  // (ROW, NQB = 8: dP from the query-major -D, for the parked dS^T)
+      if constexpr (KSLOT8) {
+        const f32x4 ndq = *reinterpret_cast<const f32x4*>(
+            reinterpret_cast<const float*>(smem + Lay::NDQ_OFF) + lq0);
+#pragma unroll
+        for (int k2 = 0; k2 < 2; ++k2) {
+          dPq[k2] = mfma16(da0, vf[k2][0], ndq);
+          dPq[k2] = mfma16(da1, vf[k2][1], dPq[k2]);
+        }
       }
       // lane holds X[q = q0 + r][key = kb + k2*16 + t]
 #pragma unroll
@@ -745,14 +848,18 @@ attn_bwd_kernel(int n_items, int L, int H, int D, const bf16_t* __restrict__ qkv
         sw[k2][2 * qt] = pack2bf(ds[0], ds[1]);
         sw[k2][2 * qt + 1] = pack2bf(ds[2], ds[3]);
         // park dS^T[key][q0..q0+3] for the dQ phase
-        *reinterpret_cast<uint2*>(dSTs + (kb + k2 * 16 + t) * Lay::DST_STRIDE + q0 * 2) =
-            uint2{sw[k2][2 * qt], sw[k2][2 * qt + 1]};
+        uint2 park = uint2{sw[k2][2 * qt], sw[k2][2 * qt + 1]};
+        if constexpr (KSLOT8) {
+          const f32x4 dsq = p * dPq[k2];
+          park = uint2{pack2bf(dsq[0], dsq[1]), pack2bf(dsq[2], dsq[3])};
+        }
+        *reinterpret_cast<uint2*>(dSTs + (kb + k2 * 16 + t) * Lay::DST_STRIDE + lq0 * 2) = park;
       }
     }
     const bf16x8 pB[2] = {as_bf8(pw[0]), as_bf8(pw[1])};
     const bf16x8 sB[2] = {as_bf8(sw[0]), as_bf8(sw[1])};
-    const char* qblk = Qs + qc * 32 * 128;
-    const char* dblk = dOs + qc * 32 * 128;
+    const char* qblk = Qs + lq * 128;
+    const char* dblk = dOs + lq * 128;
 #pragma unroll
     for (int dt = 0; dt < 4; ++dt) {
       const bf16x8 doT = cat4(lds_tr(dblk + tro[dt]), lds_tr(dblk + 16 * 128 + tro[dt]));
@@ -793,25 +900,26 @@ attn_bwd_kernel(int n_items, int L, int H, int D, const bf16_t* __restrict__ qkv
 
   // phase 2: dQ^T[d][q] = sum_key K^T[d][key] dS^T[key][q] for queries qb..qb+31 (k order:
   // key = 32s + 8g + j, from rows 8g+(t>>2) and 8g+4+(t>>2) of both images)
+  // (ROW: the live chunk's wave alone; its dS^T columns start at 0. R_MUL / R_STEP: see ROW)
   const int qb = 32 * w;
-  const int s_end = causal ? min(NQB, w + 1) : NQB;
+  const int s_end = (ROW && w != rowc) ? 0 : (causal ? min(NQB, w + 1) : NQB);
   int klo[4], khi[4];
 #pragma unroll
   for (int dt = 0; dt < 4; ++dt) {
     const int col = dt * 16 + (t & 3) * 4;
-    const int r0 = 8 * g + (t >> 2);
+    const int r0 = R_MUL * g + (t >> 2);
     klo[dt] = r0 * 128 + swz(r0, col >> 3) * 16 + (col & 7) * 2;
-    khi[dt] = (r0 + 4) * 128 + swz(r0 + 4, col >> 3) * 16 + (col & 7) * 2;
+    khi[dt] = (r0 + R_STEP) * 128 + swz(r0 + R_STEP, col >> 3) * 16 + (col & 7) * 2;
   }
-  const char* dst0 = dSTs + (8 * g + (t >> 2)) * Lay::DST_STRIDE + (qb + (t & 3) * 4) * 2;
+  const char* dst0 = dSTs + (R_MUL * g + (t >> 2)) * Lay::DST_STRIDE + ((ROW ? 0 : qb) + (t & 3) * 4) * 2;
   f32x4 dQ[4][2];
 #pragma unroll
   for (int dt = 0; dt < 4; ++dt) dQ[dt][0] = dQ[dt][1] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll 1
   for (int s = 0; s < s_end; ++s) {
     const char* ds = dst0 + 32 * s * Lay::DST_STRIDE;
-    const bf16x8 bq0 = cat4(lds_tr(ds), lds_tr(ds + 4 * Lay::DST_STRIDE));
-    const bf16x8 bq1 = cat4(lds_tr(ds + 32), lds_tr(ds + 4 * Lay::DST_STRIDE + 32));
+    const bf16x8 bq0 = cat4(lds_tr(ds), lds_tr(ds + R_STEP * Lay::DST_STRIDE));
+    const bf16x8 bq1 = cat4(lds_tr(ds + 32), lds_tr(ds + R_STEP * Lay::DST_STRIDE + 32));
     const char* kblk = Ks + 32 * s * 128;
 #pragma unroll
     for (int dt = 0; dt < 4; ++dt) {
@@ -1531,6 +1639,35 @@ int lc_attn_bwd(hipStream_t st, int n_seq, int L, int H, const void* qkv, long l
     break;
     LC_AB(1) LC_AB(2) LC_AB(3) LC_AB(4) LC_AB(5) LC_AB(6) LC_AB(7)
 #undef LC_AB
+    default:
+      return LC_EINVAL;
+  }
+  LC_LAUNCH_RET();
+}
+
+int lc_attn_bwd_live_row(hipStream_t st, int n_seq, int L, int H, const void* qkv, long ldq,
+                         int row, const void* O_row, const void* dO_row, long ldo,
+                         const float* lse_row, void* dqkv, long lddq, int causal) {
+  LC_CHECK_ARG(n_seq > 0 && L > 0 && L <= 256 && H > 0 && row >= 0 && row < L);
+  LC_CHECK_ARG(ldq >= 3 * H * 64 && ldo >= H * 64 && lddq >= 3 * H * 64 && ldq % 8 == 0 &&
+               ldo % 8 == 0 && lddq % 8 == 0 && ((uintptr_t)O_row & 15) == 0 &&
+               ((uintptr_t)dO_row & 15) == 0 && ((uintptr_t)dqkv & 15) == 0 &&
+               (long)L * ldq * 2 < 0x7ffffff0L && (long)L * lddq * 2 < 0x7ffffff0L);
+  // the result is the default form's (fused kernel; key-major + query-major pair at 8 chunks)
+  if (g_attn_bwd_form != 0 && g_attn_bwd_form != ATTN_BWD_FUSED) return LC_EUNSUPPORTED;
+  const int D = H * 64;
+  switch ((L + 31) / 32) {
+#define LC_ABR(Q)                                                                               \
+  case Q:                                                                                      \
+    hipLaunchKernelGGL((attn_bwd_kernel<Q, (Q >= 5), false, true>),                            \
+                       dim3(Q >= 5 ? persistent_grid(n_seq * H, BwdLdsRow<Q>::BYTES)           \
+                                   : n_seq * H),                                               \
+                       dim3(64 * Q), 0, st, n_seq * H, L, H, D, (const bf16_t*)qkv, ldq,       \
+                       (const bf16_t*)O_row, (const bf16_t*)dO_row, ldo, lse_row,              \
+                       (bf16_t*)dqkv, lddq, causal, 0.125f, (uint8_t*)nullptr, (long)row);     \
+    break;
+    LC_ABR(1) LC_ABR(2) LC_ABR(3) LC_ABR(4) LC_ABR(5) LC_ABR(6) LC_ABR(7) LC_ABR(8)
+#undef LC_ABR
     default:
       return LC_EINVAL;
   }

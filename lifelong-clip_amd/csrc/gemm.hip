@@ -99,6 +99,10 @@ LC_DEV void wait_vmcnt() {
   asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
 }
 
+// The value every epilogue starts from: accumulator x alpha + bias (store_tile and the row
+// fix-up of lc_gemm_nt_rows share it, so the two cannot round differently).
+LC_DEV float epi_affine(float acc, float alpha, float bias) { return acc * alpha + bias; }
+
 // Epilogue shared by the GEMM kernels: acc holds the swapped MFMA layout (lane: 4 consecutive
 // columns n of one row m per 16x16 subtile).
 template <int BM, int BN, int WM, int WN, int EPI, int PASS_MAX = 32, int TM, int TN>
@@ -276,7 +280,7 @@ LC_DEV void store_tile(f32x4 (&acc)[TM][TN], char* smem, int smem_bytes, int m0,
       for (int q = 0; q < NQ; ++q) {
         const f32x4 a4 = *reinterpret_cast<const f32x4*>(stg + lr * LSTR + lc + 4 * q);
 #pragma unroll
-        for (int r = 0; r < 4; ++r) v[4 * q + r] = a4[r] * alpha + bb[4 * q + r];
+        for (int r = 0; r < 4; ++r) v[4 * q + r] = epi_affine(a4[r], alpha, bb[4 * q + r]);
       }
       const float* xf = pf_f[pass & 1][it];
       const uint32_t* xb = pf_b[pass & 1][it];
@@ -2017,6 +2021,20 @@ int launch_pp(hipStream_t st, int epi, int M, int N, int K, const bf16_t* A, lon
 
 // Phase-interleaved 256x256 GEMM (gemm8_kernel). bf16: A, B bf16 with lda/ldb in elements;
 // fp8: A, B e4m3 with lda/ldb in bytes and their E8M0 scales in sc.
+// The split-K plan of a gemm8_kernel launch (launch_g8, and lc_gemm_nt_rows for the launch it
+// stands in for).
+template <bool FP8>
+SplitK g8_plan(int M, int N, int K, void* ws, long ws_bytes) {
+  const int tiles = ((M + 255) / 256) * (N / 256);
+  const int units = K / (FP8 ? 128 : 64);
+  // (LC_GEMM_SPLIT_MIN overrides the minimum k-tiles per split-K slice: in-step A/Bs)
+  static const int split_min = [] {
+    const char* e = lc_diag_env("LC_GEMM_SPLIT_MIN");
+    return e && atoi(e) > 0 ? atoi(e) : 8;
+  }();
+  return plan_split(tiles, units, split_min, ws, ws_bytes);
+}
+
 template <bool FP8>
 int launch_g8(hipStream_t st, int epi, int M, int N, int K, const void* A, long lda,
               const void* B, long ldb, const float* bias, float alpha, void* o0, long l0,
@@ -2026,12 +2044,7 @@ int launch_g8(hipStream_t st, int epi, int M, int N, int K, const void* A, long 
   ep.group_m = group_m(N);
   const int tiles = ((M + 255) / 256) * (N / 256);
   const int units = K / (FP8 ? 128 : 64);
-  // (LC_GEMM_SPLIT_MIN overrides the minimum k-tiles per split-K slice: in-step A/Bs)
-  static const int split_min = [] {
-    const char* e = lc_diag_env("LC_GEMM_SPLIT_MIN");
-    return e && atoi(e) > 0 ? atoi(e) : 8;
-  }();
-  const SplitK sk = plan_split(tiles, units, split_min, ws, ws_bytes);
+  const SplitK sk = g8_plan<FP8>(M, N, K, ws, ws_bytes);
   const long ea = FP8 ? 1 : 2;  // bytes per element
   // the main-loop DMA descriptors span one 256-row tile of A / B with 32-bit byte offsets
   LC_CHECK_ARG(lda * ea < (1L << 23) && ldb * ea < (1L << 23));
@@ -2086,11 +2099,42 @@ int launch_g8(hipStream_t st, int epi, int M, int N, int K, const void* A, long 
 int g_force_tile = -1;
 unsigned long long* g_dbg = nullptr;
 
+int forced_tile() {
+  if (g_force_tile < 0) {
+    const char* e = lc_diag_env("LC_GEMM_TILE");
+    g_force_tile = e ? atoi(e) : 0;
+  }
+  return g_force_tile;
+}
+
+// the epilogues gemm8_kernel is instantiated for (the others of tile 8 run on the ping-pong kernel)
+bool g8_epilogue(int epi) {
+  return epi == EPI_BF16 || epi == EPI_F32 || epi == EPI_RESID || epi == EPI_GELU ||
+         epi == EPI_GELU_D || epi == EPI_MUL || epi == EPI_RESID16;
+}
+
+#ifndef LC_F16
+#ifndef LC_BLASLT_MIN_M  // (A/B builds override it)
+#define LC_BLASLT_MIN_M 32768
+#endif
+// the QKV input-gradient GEMM of a 256-image step (plain: no epilogue, no bias) on hipBLASLt
+// (blaslt.hip: 142 vs 160 us standalone, step +1.2 %); its workspace is the split-K scratch
+// after the tickets. A forced tile (A/B tools) or LC_GEMM_BLASLT=0 (DIAG) keeps gemm8.
+bool blaslt_wanted(int tile, int epi, const float* bias, float alpha, int M, int N, int K,
+                   const void* ws, long ws_bytes) {
+  static const bool use_blaslt = [] {
+    const char* e = lc_diag_env("LC_GEMM_BLASLT");
+    return !(e && e[0] == '0');
+  }();
+  return use_blaslt && tile == 0 && epi == EPI_BF16 && bias == nullptr && alpha == 1.0f &&
+         M >= LC_BLASLT_MIN_M && N == 768 && K == 2304 && ws != nullptr &&
+         ws_bytes >= LC_SPLITK_TICKET_BYTES + (8L << 20);
+}
+#endif
+
+int route_tile(int tile, int epi, int M, int N, int K);
+
 }  // namespace
-
-extern "C" {
-
-}  // extern "C"
 
 int lc_gemm_nt_ex(hipStream_t stream, int epi, int M, int N, int K, const void* A, long lda,
                   const void* B, long ldb, const float* bias, float alpha, void* out0, long ldo0,
@@ -2112,30 +2156,53 @@ int lc_gemm_nt_ex(hipStream_t stream, int epi, int M, int N, int K, const void* 
   if (epi == EPI_AD_UP) LC_CHECK_ARG(ep.aux2 != nullptr && ep.ldaux2 >= N && ep.ldaux2 % 8 == 0);
   auto a = static_cast<const bf16_t*>(A);
   auto b = static_cast<const bf16_t*>(B);
-  if (g_force_tile < 0) {
-    const char* e = lc_diag_env("LC_GEMM_TILE");
-    g_force_tile = e ? atoi(e) : 0;
-  }
-  int tile = g_force_tile;
+  int tile = forced_tile();
 #ifndef LC_F16
-#ifndef LC_BLASLT_MIN_M  // (A/B builds override it)
-#define LC_BLASLT_MIN_M 32768
-#endif
-  // the QKV input-gradient GEMM of a 256-image step (plain: no epilogue, no bias) on hipBLASLt
-  // (blaslt.hip: 142 vs 160 us standalone, step +1.2 %); its workspace is the split-K scratch
-  // after the tickets. A forced tile (A/B tools) or LC_GEMM_BLASLT=0 (DIAG) keeps gemm8.
-  static const bool use_blaslt = [] {
-    const char* e = lc_diag_env("LC_GEMM_BLASLT");
-    return !(e && e[0] == '0');
-  }();
-  if (use_blaslt && tile == 0 && epi == EPI_BF16 && bias == nullptr && alpha == 1.0f &&
-      M >= LC_BLASLT_MIN_M && N == 768 && K == 2304 && ws != nullptr &&
-      ws_bytes >= LC_SPLITK_TICKET_BYTES + (8L << 20) &&
+  if (blaslt_wanted(tile, epi, bias, alpha, M, N, K, ws, ws_bytes) &&
       lc_blaslt_nt_bf16(stream, M, N, K, a, lda, b, ldb, out0, ldo0,
                         static_cast<char*>(ws) + LC_SPLITK_TICKET_BYTES,
                         ws_bytes - LC_SPLITK_TICKET_BYTES))
     return LC_OK;
 #endif
+  tile = route_tile(tile, epi, M, N, K);
+  switch (tile) {
+    case 1:
+      return launch_nt<128, 128, 2, 2, 2>(stream, epi, M, N, K, a, lda, b, ldb, bias, alpha, out0,
+                                          ldo0, out1, ldo1, aux, ldaux, ep);
+    case 2:
+      return launch_nt<256, 128, 4, 2, 3>(stream, epi, M, N, K, a, lda, b, ldb, bias, alpha, out0,
+                                          ldo0, out1, ldo1, aux, ldaux, ep);
+    case 3:
+      return launch_nt<256, 256, 2, 4, 2>(stream, epi, M, N, K, a, lda, b, ldb, bias, alpha, out0,
+                                          ldo0, out1, ldo1, aux, ldaux, ep);
+    case 7:
+      return launch_w4(stream, epi, M, N, K, a, lda, b, ldb, bias, alpha, out0, ldo0, out1, ldo1,
+                       aux, ldaux, ep);
+    case 5:
+    case 6:
+      return launch_pp(stream, epi, M, N, K, a, lda, b, ldb, bias, alpha, out0, ldo0, out1, ldo1,
+                       aux, ldaux, ep, ws, ws_bytes);
+    case 8:
+      if (!g8_epilogue(epi))
+        return launch_pp(stream, epi, M, N, K, a, lda, b, ldb, bias, alpha, out0, ldo0, out1, ldo1,
+                         aux, ldaux, ep, ws, ws_bytes);
+      return launch_g8<false>(stream, epi, M, N, K, a, lda, b, ldb, bias, alpha, out0, ldo0, out1,
+                              ldo1, aux, ldaux, ep, ws, ws_bytes, Fp8Scales{});
+    case 11:  // 128x64, one LDS stage
+      return launch_nt<128, 64, 4, 1, 1>(stream, epi, M, N, K, a, lda, b, ldb, bias, alpha, out0,
+                                         ldo0, out1, ldo1, aux, ldaux, ep);
+    default:
+      return launch_nt<128, 64, 4, 1, 2>(stream, epi, M, N, K, a, lda, b, ldb, bias, alpha, out0,
+                                         ldo0, out1, ldo1, aux, ldaux, ep);
+  }
+}
+
+namespace {
+
+// The kernel family lc_gemm_nt_ex runs a launch on (the lc_gemm_set_tile numbering): a forced
+// tile as it is, otherwise chosen from the shape. Shared with lc_gemm_nt_rows, which has to know
+// what a launch of M_full rows would have run on.
+int route_tile(int tile, int epi, int M, int N, int K) {
   if (tile == 0) {
     // measured on the ViT-B/16 step shapes (tools/bench_gemm.py, M = 50 432): the 256x256
     // phase-interleaved kernel beats the ping-pong one on every shape (776-1113 vs 743-1044 TF)
@@ -2184,40 +2251,136 @@ int lc_gemm_nt_ex(hipStream_t stream, int epi, int M, int N, int K, const void* 
   if (((tile == 3 || tile == 5 || tile == 6 || tile == 7 || tile == 8) && N % 256) ||
       ((tile == 1 || tile == 2) && N % 128))
     tile = 4;
-  switch (tile) {
-    case 1:
-      return launch_nt<128, 128, 2, 2, 2>(stream, epi, M, N, K, a, lda, b, ldb, bias, alpha, out0,
-                                          ldo0, out1, ldo1, aux, ldaux, ep);
-    case 2:
-      return launch_nt<256, 128, 4, 2, 3>(stream, epi, M, N, K, a, lda, b, ldb, bias, alpha, out0,
-                                          ldo0, out1, ldo1, aux, ldaux, ep);
-    case 3:
-      return launch_nt<256, 256, 2, 4, 2>(stream, epi, M, N, K, a, lda, b, ldb, bias, alpha, out0,
-                                          ldo0, out1, ldo1, aux, ldaux, ep);
-    case 7:
-      return launch_w4(stream, epi, M, N, K, a, lda, b, ldb, bias, alpha, out0, ldo0, out1, ldo1,
-                       aux, ldaux, ep);
-    case 5:
-    case 6:
-      return launch_pp(stream, epi, M, N, K, a, lda, b, ldb, bias, alpha, out0, ldo0, out1, ldo1,
-                       aux, ldaux, ep, ws, ws_bytes);
-    case 8:
-      if (epi != EPI_BF16 && epi != EPI_F32 && epi != EPI_RESID && epi != EPI_GELU &&
-          epi != EPI_GELU_D && epi != EPI_MUL && epi != EPI_RESID16)
-        return launch_pp(stream, epi, M, N, K, a, lda, b, ldb, bias, alpha, out0, ldo0, out1, ldo1,
-                         aux, ldaux, ep, ws, ws_bytes);
-      return launch_g8<false>(stream, epi, M, N, K, a, lda, b, ldb, bias, alpha, out0, ldo0, out1,
-                              ldo1, aux, ldaux, ep, ws, ws_bytes, Fp8Scales{});
-    case 11:  // 128x64, one LDS stage
-      return launch_nt<128, 64, 4, 1, 1>(stream, epi, M, N, K, a, lda, b, ldb, bias, alpha, out0,
-                                         ldo0, out1, ldo1, aux, ldaux, ep);
-    default:
-      return launch_nt<128, 64, 4, 1, 2>(stream, epi, M, N, K, a, lda, b, ldb, bias, alpha, out0,
-                                         ldo0, out1, ldo1, aux, ldaux, ep);
+  return tile;
+}
+
+// What a launch lc_gemm_nt_ex(epi, M, N, K, bias, alpha, ws) would run as, for lc_gemm_nt_rows
+// and lc_gemm_split_plan. ok: a schedule the row form can stand in for — gemm8_kernel's default
+// schedule with the returned plan, or a kernel family without any split (dp_tiles = every
+// 256x256 tile, S = 1: a launch at fewer rows sums each row in the same order). Not ok: a
+// forced tile, a stream-K mode, hipBLASLt, the ping-pong kernel (its own split rule).
+struct FullRoute {
+  bool ok;
+  SplitK sk;
+  int group_m;
+};
+FullRoute full_route(int epi, const float* bias, float alpha, int M, int N, int K, void* ws,
+                     long ws_bytes) {
+  FullRoute r{false, SplitK{((M + 255) / 256) * ((N + 255) / 256), 1, nullptr, nullptr}, 1};
+  if (forced_tile() != 0 || g_sk_mode != 0) return r;
+#ifndef LC_F16
+  if (blaslt_wanted(0, epi, bias, alpha, M, N, K, ws, ws_bytes)) return r;
+#endif
+  const int tile = route_tile(0, epi, M, N, K);
+  if (tile == 5 || tile == 6 || (tile == 8 && !g8_epilogue(epi))) return r;
+  r.ok = true;
+  if (tile == 8) {
+    r.sk = g8_plan<false>(M, N, K, ws, ws_bytes);
+    r.group_m = group_m(N);
+  }
+  return r;
+}
+
+// Row fix-up of lc_gemm_nt_rows. Workgroup x takes the full launch's split-K tail tile
+// dp_tiles + x, finds its place with the launch's own raster (tile_coords) and rewrites the
+// compact rows i whose full-launch row i * mul + add lies in that tile: the S slice partials
+// part[s][i][:] (f32, [S][n][N]) summed in the tail's order, then the epilogue's arithmetic.
+// 64 lanes x 4 columns cover the tile's 256 columns, 4 rows per pass.
+template <int EPI>
+__global__ void __launch_bounds__(256)
+gemm_rows_fixup_kernel(int n, int N, int M_full, long mul, long add, int gm, int dp_tiles, int S,
+                       const float* __restrict__ part, const float* __restrict__ bias,
+                       float alpha, void* __restrict__ out, long ldo) {
+  static_assert(EPI == EPI_BF16 || EPI == EPI_F32, "plain epilogues only");
+  int tm, tn;
+  tile_coords(dp_tiles + (int)blockIdx.x, (M_full + 255) / 256, N / 256, gm, tm, tn);
+  const long lo = (long)tm * 256, hi = min(lo + 256, (long)M_full);
+  // compact rows [i0, i1): the first i with i * mul + add >= lo, resp. >= hi
+  const long i0 = lo <= add ? 0 : (lo - add + mul - 1) / mul;
+  const long i1 = min((long)n, hi <= add ? 0 : (hi - add + mul - 1) / mul);
+  const int col = tn * 256 + (threadIdx.x & 63) * 4;
+  f32x4 bb = f32x4{0.f, 0.f, 0.f, 0.f};
+  if (bias != nullptr) bb = *reinterpret_cast<const f32x4*>(bias + col);
+  for (long i = i0 + (threadIdx.x >> 6); i < i1; i += 4) {
+    f32x4 p[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+      p[k] = k < S ? *reinterpret_cast<const f32x4*>(part + ((long)k * n + i) * N + col)
+                   : f32x4{0.f, 0.f, 0.f, 0.f};
+    // splitk_sum's order (gemm8_kernel's body stays as it is, so the loop is repeated here):
+    // zero, then the four slice slots one after another, zero for k >= S
+    f32x4 sum = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int k = 0; k < 4; ++k) sum += p[k];
+    float v[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) v[r] = epi_affine(sum[r], alpha, bb[r]);
+    if constexpr (EPI == EPI_BF16)
+      *reinterpret_cast<lc_u32x2*>(static_cast<bf16_t*>(out) + i * ldo + col) =
+          lc_u32x2{pack2bf(v[0], v[1]), pack2bf(v[2], v[3])};
+    else
+      *reinterpret_cast<f32x4*>(static_cast<float*>(out) + i * ldo + col) =
+          f32x4{v[0], v[1], v[2], v[3]};
   }
 }
 
+}  // namespace
+
 extern "C" {
+
+int lc_gemm_split_plan(int M, int N, int K, long ws_bytes, int* dp_tiles, int* splits) {
+  LC_CHECK_ARG(M > 0 && N > 0 && K > 0 && K % 64 == 0 && N % 64 == 0 && dp_tiles && splits);
+  // (the plan only does arithmetic on the workspace pointer: any non-null one serves)
+  char dummy;
+  const FullRoute r = full_route(EPI_F32, nullptr, 1.0f, M, N, K,
+                                 ws_bytes > 0 ? &dummy : nullptr, ws_bytes);
+  if (!r.ok) return LC_EUNSUPPORTED;
+  *dp_tiles = r.sk.dp_tiles;
+  *splits = r.sk.splits;
+  return LC_OK;
+}
+
+int lc_gemm_nt_rows(hipStream_t stream, int epi, int n, int N, int K, const void* A, long lda,
+                    const void* B, long ldb, const float* bias, float alpha, void* out, long ldo,
+                    int M_full, long mul, long add, void* ws, long ws_bytes) {
+  LC_CHECK_ARG(n > 0 && N > 0 && K > 0 && K % 64 == 0 && N % 64 == 0 && M_full > 0);
+  LC_CHECK_ARG(mul >= 1 && add >= 0 && (long)(n - 1) * mul + add < (long)M_full);
+  LC_CHECK_ARG(ws == nullptr || (ws_bytes >= LC_SPLITK_TICKET_BYTES && ((uintptr_t)ws & 255) == 0));
+  LC_CHECK_ARG(out != nullptr && ((uintptr_t)out & 15) == 0 && ldo % 8 == 0 && ldo >= N);
+  LC_CHECK_ARG(bias == nullptr || ((uintptr_t)bias & 15) == 0);
+  if ((epi != EPI_BF16 && epi != EPI_F32) || alpha != 1.0f) return LC_EUNSUPPORTED;
+  const FullRoute r = full_route(epi, bias, alpha, M_full, N, K, ws, ws_bytes);
+  if (!r.ok) return LC_EUNSUPPORTED;
+  const int S = r.sk.splits, nt = K / 64;
+  const int tiles = ((M_full + 255) / 256) * (N / 256);
+  float* part = nullptr;
+  if (S > 1) {
+    // the slice partials go where the full launch keeps its slabs (stream-ordered, tickets untouched)
+    if (LC_SPLITK_TICKET_BYTES + (long)S * n * N * 4 > ws_bytes) return LC_EUNSUPPORTED;
+    part = reinterpret_cast<float*>(static_cast<char*>(ws) + LC_SPLITK_TICKET_BYTES);
+  }
+  const EpiParams ep{nullptr, 0, 1.0f, 1.0f, 0, g_dbg};
+  // every row as a launch without a split sums it; no workspace: this launch must not split
+  int rc = lc_gemm_nt_ex(stream, epi, n, N, K, A, lda, B, ldb, bias, alpha, out, ldo, nullptr, 0,
+                         nullptr, 0, ep, nullptr, 0);
+  if (rc != LC_OK || S == 1) return rc;
+  for (int s = 0; s < S; ++s) {  // k-tiles [tb, te) of slice s, as gemm8_kernel cuts them
+    const int tb = s * nt / S, te = (s + 1) * nt / S;
+    rc = lc_gemm_nt_ex(stream, EPI_F32, n, N, (te - tb) * 64,
+                       static_cast<const bf16_t*>(A) + (long)tb * 64, lda,
+                       static_cast<const bf16_t*>(B) + (long)tb * 64, ldb, nullptr, 1.0f,
+                       part + (long)s * n * N, N, nullptr, 0, nullptr, 0, ep, nullptr, 0);
+    if (rc != LC_OK) return rc;
+  }
+  dim3 grid(tiles - r.sk.dp_tiles), block(256);
+  if (epi == EPI_BF16)
+    hipLaunchKernelGGL((gemm_rows_fixup_kernel<EPI_BF16>), grid, block, 0, stream, n, N, M_full,
+                       mul, add, r.group_m, r.sk.dp_tiles, S, part, bias, alpha, out, ldo);
+  else
+    hipLaunchKernelGGL((gemm_rows_fixup_kernel<EPI_F32>), grid, block, 0, stream, n, N, M_full,
+                       mul, add, r.group_m, r.sk.dp_tiles, S, part, bias, alpha, out, ldo);
+  LC_LAUNCH_RET();
+}
 
 // See include/lc_clip.h for the contract.
 int lc_gemm_nt(hipStream_t stream, int epi, int M, int N, int K, const void* A, long lda,

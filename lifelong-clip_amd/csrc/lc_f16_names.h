@@ -9,9 +9,12 @@
 #define lc_attn_bwd_set_form lc_attn_bwd_set_form_f16
 #define lc_attn_row_fwd lc_attn_row_fwd_f16
 #define lc_attn_row_bwd lc_attn_row_bwd_f16
+#define lc_attn_bwd_live_row lc_attn_bwd_live_row_f16
 #define lc_gemm_nt_ex lc_gemm_nt_ex_f16
 #define lc_gemm_nt lc_gemm_nt_f16
 #define lc_gemm_nt_ws lc_gemm_nt_ws_f16
+#define lc_gemm_nt_rows lc_gemm_nt_rows_f16
+#define lc_gemm_split_plan lc_gemm_split_plan_f16
 #define lc_gemm_set_debug lc_gemm_set_debug_f16
 #define lc_gemm_nt_fp8 lc_gemm_nt_fp8_f16
 #define lc_gemm_set_tile lc_gemm_set_tile_f16

@@ -22,6 +22,9 @@ SIGNATURES = {
                    c_long, P, c_long],
     "lc_gemm_nt_ws": [P, c_int, c_int, c_int, c_int, P, c_long, P, c_long, P, c_float, P, c_long,
                       P, c_long, P, c_long, P, c_long],
+    "lc_gemm_nt_rows": [P, c_int, c_int, c_int, c_int, P, c_long, P, c_long, P, c_float, P, c_long,
+                        c_int, c_long, c_long, P, c_long],
+    "lc_gemm_split_plan": [c_int, c_int, c_int, c_long, P, P],
     "lc_gemm_nt_fp8": [P, c_int, c_int, c_int, c_int, P, c_long, P, c_long, P, c_long, P, c_long,
                        P, c_float, P, c_long, P, c_long, P, c_long, P, c_long, P, c_long],
     "lc_quant_fp8": [P, c_long, c_int, P, c_int, c_long, c_long, P, c_long, P, c_long],
@@ -48,6 +51,8 @@ SIGNATURES = {
     "lc_attn_bwd": [P, c_int, c_int, c_int, P, c_long, P, P, c_long, P, P, c_long, c_int],
     "lc_attn_row_fwd": [P, c_int, c_int, c_int, P, c_long, c_int, P, c_long, P, c_int],
     "lc_attn_row_bwd": [P, c_int, c_int, c_int, P, c_long, c_int, P, P, c_long, P, P, c_long, c_int],
+    "lc_attn_bwd_live_row": [P, c_int, c_int, c_int, P, c_long, c_int, P, P, c_long, P, P, c_long,
+                             c_int],
     "lc_attn_bwd_fp8": [P, c_int, c_int, c_int, P, c_long, P, P, c_long, P, P, c_long, P, c_long,
                         c_int],
     "lc_train_transform": [P, c_int, c_int, c_int, c_int, P, c_int, c_int, c_int, c_int, c_int, P,
@@ -105,9 +110,10 @@ SIGNATURES = {
 }
 
 # the IEEE-half (text tower) forms: same arguments (include/lc_clip.h, "IEEE-half storage")
-F16_ENTRY_POINTS = ("lc_gemm_nt", "lc_gemm_nt_ws", "lc_gemm_tn", "lc_gemm_tn_ws",
+F16_ENTRY_POINTS = ("lc_gemm_nt", "lc_gemm_nt_ws", "lc_gemm_nt_rows", "lc_gemm_tn", "lc_gemm_tn_ws",
                     "lc_layernorm_fwd", "lc_layernorm_bwd", "lc_attn_fwd", "lc_attn_bwd",
                     "lc_attn_bwd_set_form", "lc_attn_row_fwd", "lc_attn_row_bwd",
+                    "lc_attn_bwd_live_row",
                     "lc_adapter_fwd_rows", "lc_adapter_ln_fwd_rows",
                     "lc_cast_bf16", "lc_merge_weight", "lc_cast_weights_bf16",
                     "lc_merge_weights_bf16", "lc_lora_grad", "lc_lora_grad_ws", "lc_adapter_fwd",

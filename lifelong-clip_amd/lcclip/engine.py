@@ -241,6 +241,21 @@ class BlockStack:
             return ops.gemm_nt_fp8(ops.quant_fp8(A), st.q[name], epi, out0, **kw)
         return ops.gemm_nt(A, getattr(st, name), epi, out0, **kw)
 
+    # LCCLIP_ROWS_EXACT=0: the compact last block's K = 3072 GEMMs and its attention backward
+    # as full-size launches on operands blanked off the live rows again, instead of
+    # ops.gemm_nt_rows / ops.attn_bwd_live_row (A/B experiments; both give the full path's bits)
+    ROWS_EXACT = os.environ.get("LCCLIP_ROWS_EXACT", "1") != "0"
+
+    def _gemm_rows(self, st, name, A, epi, out0, M_full, mul, **kw):
+        """out0[i] = row i * mul of _gemm at M_full rows on A scattered to those rows (zero
+        elsewhere), from the compact A: True when ops.gemm_nt_rows ran it, False (nothing
+        written) when the caller has to run the full-size launch."""
+        if not self.ROWS_EXACT or (self.precision == "fp8" and name in self.FP8_WEIGHTS):
+            return False
+        if set(kw) - {"bias"}:
+            return False
+        return ops.gemm_nt_rows(A, getattr(st, name), epi, out0, M_full, mul, 0, **kw)
+
     def _stage_lora(self, st, name, A, B, merges):
         """(A_pad [64,K], Bt_pad [64,N]) bf16 with rows >= r zero, staged from A [r,K], B [N,r]
         by two casts appended to `merges` (launched with the block's weight merges). The
@@ -421,11 +436,14 @@ class BlockStack:
                 if rows and not self.ROW_BWD:
                     # K = 3072: the full-size launch sums the rows of its ragged last round of
                     # tiles split over K (gemm8's split-K tail), another f32 order than a launch
-                    # at M = n_seq. c_proj runs at full size on an operand that is zero off the
-                    # live rows, so z2 keeps the full path's bits
-                    gf, zf = self._blank_rows(tmp_g, n_seq, Lx), _empty((Mx, D), self.dt, dev)
-
+                    # at M = n_seq. ops.gemm_nt_rows sums the live rows in the full launch's
+                    # order; where it does not cover the case, c_proj runs at full size on an
+                    # operand that is zero off the live rows. Either way z2 keeps the full
+                    # path's bits
                     def wpr(epi, out0, **kw):
+                        if self._gemm_rows(st, "wpr", tmp_g[:Mr], epi, out0, Mx, Lx, **kw):
+                            return
+                        gf, zf = self._blank_rows(tmp_g, n_seq, Lx), _empty((Mx, D), self.dt, dev)
                         self._gemm(st, "wpr", gf, epi, zf, **kw)
                         out0.copy_(zf.view(n_seq, Lx, D)[:, 0])
             x_out = _empty((Mr, D), xdt, dev)
@@ -606,8 +624,9 @@ class BlockStack:
             else:
                 self._gemm(st, "wprT", dY, EPI_MUL, da[:Mr], aux=s["gd"])
                 if rows and not self.ROW_BWD:  # (K = 3072: as c_proj in the forward)
-                    self._gemm(st, "wfcT", self._blank_rows(da, n_seq, Lx), EPI_BF16, dh[:Mx])
-                    dh[:Mr] = dh[:Mx].view(n_seq, Lx, D)[:, 0].clone()
+                    if not self._gemm_rows(st, "wfcT", da[:Mr], EPI_BF16, dh[:Mr], Mx, Lx):
+                        self._gemm(st, "wfcT", self._blank_rows(da, n_seq, Lx), EPI_BF16, dh[:Mx])
+                        dh[:Mr] = dh[:Mx].view(n_seq, Lx, D)[:, 0].clone()
                 else:
                     self._gemm(st, "wfcT", da[:Mr], EPI_BF16, dh[:Mr])
             ops.layernorm_bwd(dh[:Mr], s["x_mid"], s["mean2"], s["rstd2"], blk.ln_2.weight,
@@ -632,6 +651,9 @@ class BlockStack:
                 qd = None
                 ops.attn_row_bwd(s["qkv"], s["O"], dO[:Mr], s["lse"], dqkv[:Mx], n_seq, Lx, H, 0,
                                  self.causal)
+            elif rows and self.ROWS_EXACT and ops.attn_bwd_live_row(
+                    s["qkv"], s["O"], dO[:Mr], s["lse"], dqkv[:Mx], n_seq, Lx, H, 0, self.causal):
+                qd = None  # (the full kernel's single-row mode: the blanked launch's dq | dk | dv)
             elif rows:
                 # the full backward kernel on its full-size operands with the dead rows blank:
                 # dO and O zero off row 0 (their rows' Delta, dP and dS are then exact zeros, as

@@ -2,9 +2,11 @@
 again in the library; every call launches on torch's current stream of the tensor's device."""
 from __future__ import annotations
 
+import ctypes
+
 import torch
 
-from ._lib import call, ptr, stream_of
+from ._lib import LcError, call, load, ptr, stream_of
 
 BF16 = torch.bfloat16
 F16 = torch.float16
@@ -80,6 +82,52 @@ def gemm_nt(A, B, epi, out0, bias=None, alpha=1.0, out1=None, aux=None):
          out1.stride(0) if out1 is not None else 0, ptr(aux), aux.stride(0) if aux is not None else 0,
          ptr(ws), ws.numel() if ws is not None else 0)
     return out0
+
+
+EUNSUPPORTED = -3  # LC_EUNSUPPORTED
+
+
+def gemm_nt_rows(A, B, epi, out0, M_full, mul, add=0, bias=None, alpha=1.0):
+    """out0[i] = row i * mul + add of gemm_nt at M_full rows whose A is zero off those rows, bit
+    for bit, from the compact A [n, K] (lc_gemm_nt_rows: the full launch's split-K tail rows
+    summed slice by slice). Returns False, with nothing launched or written, where the entry
+    point does not cover the case (another epilogue, the hipBLASLt shape, a stream-K mode, a
+    library without it): the caller then runs the full-size launch."""
+    _rowmajor(A, HALF, "A")
+    _rowmajor(B, HALF, "B")
+    _rowmajor(out0, F32 if epi == EPI_F32 else HALF, "out0")
+    if B.dtype != A.dtype:
+        raise TypeError("gemm_nt_rows: A and B must share the 16-bit type")
+    n, K = A.shape
+    N = B.shape[0]
+    if B.shape[1] != K or out0.shape[0] != n or out0.shape[1] != N:
+        raise ValueError(f"gemm_nt_rows shapes A{tuple(A.shape)} B{tuple(B.shape)} "
+                         f"out{tuple(out0.shape)}")
+    if bias is not None and (bias.dtype != F32 or bias.numel() != N or not bias.is_contiguous()):
+        raise ValueError("gemm_nt_rows bias must be a contiguous f32 vector of length N")
+    name = _sym16("lc_gemm_nt_rows", A, out0)
+    fn = getattr(load(), name, None)
+    if fn is None or fn.argtypes is None:  # an older A/B library
+        return False
+    # the workspace the full launch would get (its split plan depends on it)
+    ws = splitk_workspace(torch.cuda.current_stream(A.device)) if M_full >= 4096 else None
+    rc = fn(stream_of(A), epi, n, N, K, ptr(A), A.stride(0), ptr(B), B.stride(0), ptr(bias),
+            float(alpha), ptr(out0), out0.stride(0), M_full, mul, add, ptr(ws),
+            ws.numel() if ws is not None else 0)
+    if rc == EUNSUPPORTED:
+        return False
+    if rc != 0:
+        raise LcError(f"{name} returned {rc}")
+    return True
+
+
+def gemm_split_plan(M, N, K):
+    """(dp_tiles, S) of gemm_nt's 256x256 launch at these sizes with ops' workspace: tiles
+    [0, dp_tiles) run whole, the others are cut into S slices along K (S = 1: no split)."""
+    dp, s = ctypes.c_int(0), ctypes.c_int(0)
+    call("lc_gemm_split_plan", M, N, K, SPLITK_WS_BYTES if M >= 4096 else 0, ctypes.byref(dp),
+         ctypes.byref(s))
+    return dp.value, s.value
 
 
 # ------------------------------------------------------------------ block-scaled fp8 operands
@@ -371,6 +419,34 @@ def attn_row_bwd(qkv, O_row, dO_row, lse_row, dqkv, n_seq, L, H, row, causal):
          qkv.stride(0), int(row), ptr(O_row), ptr(dO_row), O_row.stride(0), ptr(lse_row), ptr(dqkv),
          dqkv.stride(0), int(causal))
     return dqkv
+
+
+def attn_bwd_live_row(qkv, O_row, dO_row, lse_row, dqkv, n_seq, L, H, row, causal):
+    """attn_bwd on full-size operands blanked off row `row` of every sequence (O, dO zero and
+    lse = 1e30 there), from the compact O_row / dO_row / lse_row, element for element
+    (lc_attn_bwd_live_row: the MFMA backward kernel's single-row mode). Returns False, nothing
+    launched, where the library does not cover the case: the caller then blanks and runs
+    attn_bwd."""
+    if O_row.stride(0) != dO_row.stride(0):
+        raise ValueError("O_row and dO_row must share a row stride")
+    if len({t.dtype for t in (qkv, O_row, dO_row, dqkv)}) != 1 or qkv.dtype not in HALF:
+        raise TypeError("attn_bwd_live_row: qkv, O_row, dO_row and dqkv must share the 16-bit type")
+    if tuple(O_row.shape) != (n_seq, H * 64) or tuple(dO_row.shape) != (n_seq, H * 64) \
+            or O_row.stride(1) != 1 or dO_row.stride(1) != 1 or lse_row.numel() != n_seq * H \
+            or lse_row.dtype != F32 or not lse_row.is_contiguous() \
+            or qkv.shape[0] != n_seq * L or tuple(dqkv.shape) != (n_seq * L, 3 * H * 64):
+        raise ValueError("attn_bwd_live_row: shape mismatch")
+    name = _sym16("lc_attn_bwd_live_row", qkv, O_row, dO_row, dqkv)
+    fn = getattr(load(), name, None)
+    if fn is None or fn.argtypes is None:  # an older A/B library
+        return False
+    rc = fn(stream_of(qkv), n_seq, L, H, ptr(qkv), qkv.stride(0), int(row), ptr(O_row),
+            ptr(dO_row), O_row.stride(0), ptr(lse_row), ptr(dqkv), dqkv.stride(0), int(causal))
+    if rc == EUNSUPPORTED:
+        return False
+    if rc != 0:
+        raise LcError(f"{name} returned {rc}")
+    return True
 
 
 def attn_bwd_fp8(qkv, O, dO, lse, q, n_seq, L, H, causal):
