@@ -50,6 +50,10 @@ def _rows(t, n):
     return None if t is None else t[:n]
 
 
+def _same_storage(a, b):
+    return a.untyped_storage().data_ptr() == b.untyped_storage().data_ptr()
+
+
 def _key(*tensors):
     return tuple((t.data_ptr(), t._version) for t in tensors if t is not None)
 
@@ -85,6 +89,7 @@ class BlockStack:
         self.seed_dev = None
         self.precision = "bf16"  # 'bf16' | 'fp8' (QKV / c_fc / c_proj on the fp8 MFMA)
         self.dt = BF16  # 16-bit storage of activations, gradients and staged weights
+        self._gs = self._gscale = None  # backward()'s side stream and half-gradient scale
 
     def set_storage(self, dtype):
         """16-bit storage type of the stack: torch.bfloat16 (default) or torch.float16 (IEEE
@@ -240,21 +245,6 @@ class BlockStack:
         if self.precision == "fp8" and name in self.FP8_WEIGHTS:
             return ops.gemm_nt_fp8(ops.quant_fp8(A), st.q[name], epi, out0, **kw)
         return ops.gemm_nt(A, getattr(st, name), epi, out0, **kw)
-
-    # LCCLIP_ROWS_EXACT=0: the compact last block's K = 3072 GEMMs and its attention backward
-    # as full-size launches on operands blanked off the live rows again, instead of
-    # ops.gemm_nt_rows / ops.attn_bwd_live_row (A/B experiments; both give the full path's bits)
-    ROWS_EXACT = os.environ.get("LCCLIP_ROWS_EXACT", "1") != "0"
-
-    def _gemm_rows(self, st, name, A, epi, out0, M_full, mul, **kw):
-        """out0[i] = row i * mul of _gemm at M_full rows on A scattered to those rows (zero
-        elsewhere), from the compact A: True when ops.gemm_nt_rows ran it, False (nothing
-        written) when the caller has to run the full-size launch."""
-        if not self.ROWS_EXACT or (self.precision == "fp8" and name in self.FP8_WEIGHTS):
-            return False
-        if set(kw) - {"bias"}:
-            return False
-        return ops.gemm_nt_rows(A, getattr(st, name), epi, out0, M_full, mul, 0, **kw)
 
     def _stage_lora(self, st, name, A, B, merges):
         """(A_pad [64,K], Bt_pad [64,N]) bf16 with rows >= r zero, staged from A [r,K], B [N,r]
@@ -432,20 +422,9 @@ class BlockStack:
                     ops.layernorm_fwd(x_mid, blk.ln_2.weight, blk.ln_2.bias, th, mean2, rstd2)
                 self._gemm(st, "wfc", th, EPI_GELU_D if save else EPI_GELU, pre,
                            bias=blk.mlp.c_fc.bias, out1=tmp_g[:Mr])
-                wpr = lambda epi, out0, **kw: self._gemm(st, "wpr", tmp_g[:Mr], epi, out0, **kw)  # noqa: E731
-                if rows and not self.ROW_BWD:
-                    # K = 3072: the full-size launch sums the rows of its ragged last round of
-                    # tiles split over K (gemm8's split-K tail), another f32 order than a launch
-                    # at M = n_seq. ops.gemm_nt_rows sums the live rows in the full launch's
-                    # order; where it does not cover the case, c_proj runs at full size on an
-                    # operand that is zero off the live rows. Either way z2 keeps the full
-                    # path's bits
-                    def wpr(epi, out0, **kw):
-                        if self._gemm_rows(st, "wpr", tmp_g[:Mr], epi, out0, Mx, Lx, **kw):
-                            return
-                        gf, zf = self._blank_rows(tmp_g, n_seq, Lx), _empty((Mx, D), self.dt, dev)
-                        self._gemm(st, "wpr", gf, epi, zf, **kw)
-                        out0.copy_(zf.view(n_seq, Lx, D)[:, 0])
+                wpr = lambda epi, out0, **kw: (  # noqa: E731
+                    self._gemm_rows(st, "wpr", tmp_g, epi, out0, n_seq, Lx, **kw) if rows
+                    else self._gemm(st, "wpr", tmp_g[:Mr], epi, out0, **kw))
             x_out = _empty((Mr, D), xdt, dev)
             if self.variant == "adapter":
                 ad = blk.adaptmlp
@@ -538,9 +517,10 @@ class BlockStack:
         last_rows: (g, g16) [n_seq, D] — the gradient w.r.t. the compact output of a
         forward(last_rows=True) (g16 None with a half gradient read directly). (dx, dxb) is then
         the caller's all-zero full-size pair (RowGrad): the last block's row-wise chain runs on the
-        n_seq rows, ops.attn_row_bwd writes the full dq | dk | dv, and the chain's compact result
-        is scattered into rows i * L of dx as the residual term of that block's ln_1 backward
-        (every other row of it is zero in the full computation too)."""
+        n_seq rows, _attn_bwd_rows writes the full dq | dk | dv (ops.attn_bwd_live_row; ops.attn_bwd
+        on blanked operands with ROWS_EXACT off; ops.attn_row_bwd with ROW_BWD on), and the chain's
+        compact result is scattered into rows i * L of dx as the residual term of that block's ln_1
+        backward (every other row of it is zero in the full computation too)."""
         M, D = dx.shape
         gdt = dx.dtype
         if gdt != F32 and (gscale is None or prompt_grads is not None
@@ -623,10 +603,8 @@ class BlockStack:
                 ops.gemm_nt_fp8(q, st.q["wfcT"], EPI_BF16, dh[:Mx])
             else:
                 self._gemm(st, "wprT", dY, EPI_MUL, da[:Mr], aux=s["gd"])
-                if rows and not self.ROW_BWD:  # (K = 3072: as c_proj in the forward)
-                    if not self._gemm_rows(st, "wfcT", da[:Mr], EPI_BF16, dh[:Mr], Mx, Lx):
-                        self._gemm(st, "wfcT", self._blank_rows(da, n_seq, Lx), EPI_BF16, dh[:Mx])
-                        dh[:Mr] = dh[:Mx].view(n_seq, Lx, D)[:, 0].clone()
+                if rows:
+                    self._gemm_rows(st, "wfcT", da, EPI_BF16, dh[:Mr], n_seq, Lx, scratch=dh)
                 else:
                     self._gemm(st, "wfcT", da[:Mr], EPI_BF16, dh[:Mr])
             ops.layernorm_bwd(dh[:Mr], s["x_mid"], s["mean2"], s["rstd2"], blk.ln_2.weight,
@@ -647,28 +625,8 @@ class BlockStack:
             if self.variant == "lora":
                 self._lora_grad(dY, s["O"], attn.out_proj.lora_A, attn.out_proj.lora_B,
                                 attn.scaling, grads, st.lora_out)
-            if rows and self.ROW_BWD:
-                qd = None
-                ops.attn_row_bwd(s["qkv"], s["O"], dO[:Mr], s["lse"], dqkv[:Mx], n_seq, Lx, H, 0,
-                                 self.causal)
-            elif rows and self.ROWS_EXACT and ops.attn_bwd_live_row(
-                    s["qkv"], s["O"], dO[:Mr], s["lse"], dqkv[:Mx], n_seq, Lx, H, 0, self.causal):
-                qd = None  # (the full kernel's single-row mode: the blanked launch's dq | dk | dv)
-            elif rows:
-                # the full backward kernel on its full-size operands with the dead rows blank:
-                # dO and O zero off row 0 (their rows' Delta, dP and dS are then exact zeros, as
-                # with the full path's dO = 0) and lse = 1e30 there (P = 0, the kernel's own value
-                # for padded rows), so dq | dk | dv are the full path's bit for bit. da and dh are
-                # free here (the MLP chain is done, QKV dX rewrites dh below)
-                qd = None
-                dOf, Of = da.view(-1)[:Mx * D].view(Mx, D), dh[:Mx]
-                lsef = torch.full((n_seq * H, Lx), 1e30, dtype=F32, device=dev)
-                Of.zero_()
-                Of.view(n_seq, Lx, D)[:, 0] = s["O"]
-                dOf.zero_()
-                dOf.view(n_seq, Lx, D)[:, 0] = dO[:Mr]
-                lsef[:, 0] = s["lse"]
-                ops.attn_bwd(s["qkv"], Of, dOf, lsef, dqkv[:Mx], n_seq, Lx, H, self.causal)
+            if rows:  # (da and dh are free: the MLP chain is done, QKV dX rewrites dh below)
+                qd = self._attn_bwd_rows(s, dO[:Mr], dqkv[:Mx], n_seq, Lx, da, dh)
             elif q_dqkv is not None and not first:
                 qd = ops.attn_bwd_fp8(s["qkv"], s["O"], dO[:Mx], s["lse"], q_dqkv.narrow(Mx), n_seq,
                                       Lx, H, self.causal)
@@ -688,10 +646,8 @@ class BlockStack:
                 self._gemm(st, "wqkvT", dqkv[:Mx], EPI_BF16, dh[:Mx])
             dres1 = dx_mid[:Mx]
             if rows:
-                # the caller's zero buffer with the chain's rows in place (never an output
-                # buffer: keep_input)
-                dres1 = pairs[0][0][:Mx]
-                dres1.view(n_seq, Lx, D)[:, 0] = dx_mid[:Mr]
+                # into the caller's zero buffer (never an output buffer: keep_input)
+                dres1 = self._spread(dx_mid[:Mr], n_seq, Lx, dst=pairs[0][0][:Mx], fill=None)
             if fuse_ln_q and "R" not in s and not P:
                 if out not in q_mats:
                     q_mats[out] = ops.Fp8Mat(Mmax, D, dev)
@@ -745,14 +701,13 @@ class BlockStack:
 
     def sync_grads(self):
         """Make the current stream wait for the PEFT-gradient work on the side stream."""
-        gs = getattr(self, "_gs", None)
-        if gs is not None:
-            torch.cuda.current_stream(gs.device).wait_stream(gs)
+        if self._gs is not None:
+            torch.cuda.current_stream(self._gs.device).wait_stream(self._gs)
 
     def _side(self):
         """Context for launching gradient reductions: the side stream (after the work that
         produced their inputs on the current stream) or the current stream."""
-        gs = getattr(self, "_gs", None)
+        gs = self._gs
         if gs is None:
             return _Null()
         gs.wait_stream(torch.cuda.current_stream(gs.device))
@@ -767,56 +722,101 @@ class BlockStack:
 
     def _adapter_bwd(self, blk, st, gout, h, z, keep, dz, grads, pad=None):
         """pad = (n_seq, L): gout, h and z hold row 0 of every sequence only (the compact last
-        block). Their weight-gradient launch runs on full-size operands that are zero on every
-        other row, as the full path's gradient is: the same walkers sum the same rows in the
-        same order, so these f32 gradients are the full path's bit for bit (a launch at M = n_seq
-        sums them in another order, and AdamW's first steps turn even that 3e-8 into flipped
-        16-bit weights within a few updates). Fills and launch are on the side stream."""
+        block: _wgrad_rows). The weight-gradient launch and its fills are on the side stream."""
         ad = blk.adaptmlp
         M = gout.shape[0]
         dpre = _empty((M, ad.down_size), self.dt, gout.device)
         ops.adapter_bwd(gout, h, st.wuT, st.wdT, ad.scale, keep, dpre, dz)  # dz None: dpre only
         with self._side():
-            if getattr(self, "_gs", None) is not None:
+            if self._gs is not None:
                 dpre.record_stream(self._gs)
-            if pad is not None and not self.ROW_BWD:
-                def full(t):
-                    f = torch.zeros((pad[0] * pad[1], t.shape[1]), dtype=t.dtype, device=t.device)
-                    f.view(pad[0], pad[1], -1)[:, 0] = t
-                    return f
-                gout, h, z, dpre = full(gout), full(h), full(z), full(dpre)
-            ops.adapter_wgrad(gout, h, z, dpre, ad.scale, self._grad(grads, ad.up_proj.weight),
-                              self._grad(grads, ad.up_proj.bias),
-                              self._grad(grads, ad.down_proj.weight),
-                              self._grad(grads, ad.down_proj.bias),
-                              gscale=getattr(self, "_gscale", None))
+            if pad is not None:
+                gout, h, z, dpre = self._wgrad_rows(*pad, gout, h, z, dpre)
+            ops.adapter_wgrad(gout, h, z, dpre, ad.scale, *(self._grad(grads, p) for p in (
+                ad.up_proj.weight, ad.up_proj.bias, ad.down_proj.weight, ad.down_proj.bias)),
+                gscale=self._gscale)
         return dz
 
-    # LCCLIP_HALF_GRAD_DIRECT=0: the adapter tower's half residual gradient with bf16 copies for
-    # its adapter backward launches, as before lc_adapter_*_g16 (A/B experiments)
-    HALF_GRAD_DIRECT = os.environ.get("LCCLIP_HALF_GRAD_DIRECT", "1") != "0"
-
-    # LCCLIP_ROW_BWD=1: the compact last block's attention backward on ops.attn_row_bwd (reads K
-    # and V only) and its weight gradients at M = n_seq: faster, and equal to the default up to
-    # f32 summation order. One flipped 16-bit rounding there moves the lower layers' gradients
-    # by ~1e-3 of their norm, so the default keeps the full kernels on blanked full-size
-    # operands and with them the full path's bits. A/B experiments
+    # ------------------------------------------------------------------ the compact last block
+    # forward(last_rows=True) runs the last block's row-wise part on row 0 of every sequence
+    # (n_seq rows, not n_seq * L) and keeps the full path's bits: one flipped 16-bit rounding there
+    # moves the lower layers' gradients by ~1e-3 of their norm, and 3e-8 in an f32 weight gradient
+    # is flipped 16-bit weights a few AdamW steps later. Most kernels give a row the same bits at
+    # any M. Three steps do not, because their f32 summation order depends on M: c_proj / c_fc dX
+    # (K = 3072: the full-size launch sums the rows of its ragged last round of tiles split over
+    # K, gemm8's split-K tail), the attention backward (dK / dV sum over query rows) and the
+    # adapter dW / db (sums over rows). Each has one method below that holds its whole choice:
+    #   exact (default)  a kernel that sums the live rows in the full launch's order:
+    #                    ops.gemm_nt_rows, ops.attn_bwd_live_row (weight gradients: none yet)
+    #   blanked          (ROWS_EXACT off, or the exact kernel answers "not covered") the full kernel
+    #                    on full-size operands with the live rows at rows i * L and zeros elsewhere
+    #                    (_spread), as the full path's are: the dead rows add exact zeros
+    #   rounding only    (ROW_BWD on) launches at M = n_seq and ops.attn_row_bwd: faster, equal to
+    #                    the full path up to f32 summation order. Both knobs: A/B experiments
+    ROWS_EXACT = os.environ.get("LCCLIP_ROWS_EXACT", "1") != "0"
     ROW_BWD = os.environ.get("LCCLIP_ROW_BWD", "0") == "1"
-
-    @staticmethod
-    def _blank_rows(buf, n_seq, L):
-        """buf [>= n_seq*L, W] whose first n_seq rows are the compact rows: the same buffer as
-        [n_seq*L, W] with them at rows i * L and zeros everywhere else."""
-        c = buf[:n_seq].clone()
-        f = buf[:n_seq * L]
-        f.zero_()
-        f.view(n_seq, L, -1)[:, 0] = c
-        return f
 
     def rows_ok(self):
         """forward(last_rows=True) applies: the adapter stack on bf16 / IEEE-half GEMMs (LoRA,
         the frozen prompt towers and fp8 keep every row)."""
         return self.variant == "adapter" and self.precision == "bf16"
+
+    @staticmethod
+    def _spread(src, n, L, dst=None, fill=0):
+        """src [n, W] at rows i * L of dst [n * L, W] and `fill` on the other rows (None: left as
+        they are); returns dst. dst None: a fresh buffer, on the current stream. dst may start
+        with src itself (the same buffer's first n rows: copied out first)."""
+        if dst is None:
+            dst = torch.empty((n * L, src.shape[1]), dtype=src.dtype, device=src.device)
+        elif _same_storage(src, dst):
+            src = src.clone()
+        if fill is not None:
+            dst.zero_() if fill == 0 else dst.fill_(fill)
+        dst.view(n, L, -1)[:, 0] = src
+        return dst
+
+    @staticmethod
+    def _gather(full, n, L, out):
+        """Rows i * L of full [n * L, W] into out [n, W] (full's own first n rows: cloned)."""
+        live = full.view(n, L, -1)[:, 0]
+        out.copy_(live.clone() if _same_storage(full, out) else live)
+
+    def _gemm_rows(self, st, name, buf, epi, out, n_seq, L, scratch=None, **kw):
+        """c_proj / c_fc dX: out [n_seq, D] = rows i * L of _gemm at n_seq * L rows, from the
+        compact operand in the first n_seq rows of buf [>= n_seq * L, 4D]. The blanked launch
+        spreads it within buf and writes scratch (may start with out; None: a fresh buffer)."""
+        A, Mx = buf[:n_seq], n_seq * L
+        if self.ROW_BWD:
+            self._gemm(st, name, A, epi, out, **kw)
+        elif not (self.ROWS_EXACT and not set(kw) - {"bias"} and ops.gemm_nt_rows(
+                A, getattr(st, name), epi, out, Mx, L, 0, **kw)):
+            full = out.new_empty((Mx, out.shape[1])) if scratch is None else scratch[:Mx]
+            self._gemm(st, name, self._spread(A, n_seq, L, dst=buf[:Mx]), epi, full, **kw)
+            self._gather(full, n_seq, L, out)
+
+    def _attn_bwd_rows(self, s, dO, dqkv, n_seq, L, da, dh):
+        """The full dqkv [n_seq * L, 3D] from the compact O / lse (s) and dO; returns qd (None:
+        bf16). The blanked launch borrows da / dh for dO / O: zero off row 0 (those rows' Delta, dP
+        and dS are exact zeros, as in the full path) and lse = 1e30 (P = 0, as for padded rows)."""
+        H, Mx = self.n_head, n_seq * L
+        args = (s["qkv"], s["O"], dO, s["lse"], dqkv, n_seq, L, H, 0, self.causal)
+        if self.ROW_BWD:
+            ops.attn_row_bwd(*args)
+        elif not (self.ROWS_EXACT and ops.attn_bwd_live_row(*args)):
+            Of = self._spread(s["O"], n_seq, L, dst=dh[:Mx])
+            dOf = self._spread(dO, n_seq, L, dst=da.view(-1)[:Mx * dO.shape[1]].view(Mx, -1))
+            lsef = self._spread(s["lse"].view(-1, 1), n_seq * H, L, fill=1e30).view(-1, L)
+            ops.attn_bwd(s["qkv"], Of, dOf, lsef, dqkv, n_seq, L, H, self.causal)
+
+    def _wgrad_rows(self, n_seq, L, *operands):
+        """The adapter weight-gradient operands ([n_seq, W] each) as the launch reads them:
+        blanked into fresh buffers (on the side stream under _side()), or under ROW_BWD as they
+        are. A live-rows weight-gradient walker goes here."""
+        return operands if self.ROW_BWD else tuple(self._spread(t, n_seq, L) for t in operands)
+
+    # LCCLIP_HALF_GRAD_DIRECT=0: the adapter tower's half residual gradient with bf16 copies for
+    # its adapter backward launches, as before lc_adapter_*_g16 (A/B experiments)
+    HALF_GRAD_DIRECT = os.environ.get("LCCLIP_HALF_GRAD_DIRECT", "1") != "0"
 
     def half_grad_direct(self):
         """A half residual gradient's consumers read it directly (no bf16 copies): the adapter
@@ -856,7 +856,7 @@ class BlockStack:
         M = dY.shape[0]
         r, K = A.shape
         N = B.shape[0]
-        gsc = getattr(self, "_gscale", None)  # dY carries the half residual gradient's scale
+        gsc = self._gscale  # dY carries the half residual gradient's scale
         if self._lora_1p(r, K, N):
             with self._side():
                 ops.lora_grad_1p(dY, X, a_pad, bt_pad, r, scaling, self._grad(grads, A),
@@ -867,7 +867,7 @@ class BlockStack:
         with self._side():
             xa = _empty((M, 64), self.dt, dY.device)
             dyb = _empty((M, 64), self.dt, dY.device)
-            gs = getattr(self, "_gs", None)
+            gs = self._gs
             if gs is not None:
                 xa.record_stream(gs)
                 dyb.record_stream(gs)
