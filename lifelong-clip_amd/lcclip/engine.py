@@ -16,6 +16,7 @@ layout is internal and not observable):
   attention out O   bf16 [rows, D]   kept; lse f32 [seq*H, L]
   MLP pre-activation bf16 [rows, 4D] kept (QuickGELU backward); GELU output transient
   adapter input z   bf16 [rows, D], bottleneck h bf16 [rows, 64]  kept
+What a layer keeps for its backward is one SavedLayer record (its fields name these buffers).
 Frozen weights are staged once as bf16 in both [out,in] and [in,out] layouts (forward and dX
 GEMMs are both A @ B^T); LoRA blocks re-merge W + s*B@A into those buffers each step.
 The backbone is frozen: backward produces input gradients and PEFT parameter gradients only.
@@ -30,6 +31,9 @@ from __future__ import annotations
 
 import itertools
 import os
+from collections import namedtuple
+from contextlib import nullcontext
+from types import SimpleNamespace
 
 import torch
 
@@ -58,14 +62,6 @@ def _key(*tensors):
     return tuple((t.data_ptr(), t._version) for t in tensors if t is not None)
 
 
-class _Null:
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        return False
-
-
 class StagedBlock:
     """bf16 device copies of one block's GEMM weights (both layouts)."""
 
@@ -73,6 +69,205 @@ class StagedBlock:
         self.frozen_key = None
         self.peft_key = None
         self.merge_epoch = 0  # advanced on every LoRA re-merge (part of the fp8 staging key)
+
+
+class SavedLayer:
+    """What BlockStack.forward(save=True) keeps of one layer for backward (the tensors: "Data
+    layout" in the module docstring; Mx = n_seq * (L + P) rows, Mr = Mx or, rows, n_seq)."""
+    __slots__ = (
+        "x_in",            # the layer's input at Mx rows (ln_1 backward)
+        "mean1", "rstd1",  # ln_1 statistics f32 [Mx]
+        "h1",              # ln_1 output [Mx, D]: LoRA only (in-proj dA), else None
+        "qkv", "O", "lse",  # attention operands; O [Mr, D], lse [n_seq * H, Lx] (rows: [n_seq * H])
+        "z1", "hd1",       # first adapter's input [Mr, D] and bottleneck [Mr, 64] (adapter only)
+        "x_mid",           # the attention sub-block's output [Mr, D] (ln_2 backward)
+        "mean2", "rstd2",  # ln_2 statistics f32 [Mr]
+        "gd",              # QuickGELU'(c_fc pre-activation) [Mr, 4D]
+        "z2", "hd2",       # second adapter's input and bottleneck (adapter only)
+        "keep",            # adapter dropout keep probability (1.0: no dropout)
+        "P", "inherit", "pkeep", "R",  # the layer's prompt rows (BlockStack.row_plan)
+        "rows",            # the compact last block: the row-wise part ran on the CLS rows only
+    )
+
+    def __init__(self, plan, rows=False):
+        for name in self.__slots__:
+            setattr(self, name, None)
+        self.P, self.inherit, self.pkeep, self.R = plan
+        self.rows, self.keep = rows, 1.0
+
+
+class _Rows(namedtuple("_Rows", "P inherit keep R")):
+    """One layer of BlockStack.row_plan: P rows appended (inherit: written over the rows the
+    previous layer kept), kept for the next layer, R = (row, count) replaced or None."""
+    __slots__ = ()
+
+    @property
+    def plain(self):
+        """The layer runs on its input unchanged: no rows appended or replaced."""
+        return not self.P and self.R is None
+
+
+class _GradBufs:
+    """BlockStack.backward's residual-gradient buffers: pairs of (gradient [>= Mmax, D], its
+    16-bit copy or None). pairs[0] is the caller's (dx, dxb) and is never written under
+    keep_input; pairs[1] (and [2] under keep_input) are the ping-pong partners; one more is
+    added when the first prompt layer expands.
+
+    Invariant, between layers (li the next layer to run, downwards): pairs[cur] holds the
+    gradient w.r.t. layer li's output, at L rows per sequence in its first n_seq * L rows — or,
+    when layer li kept its P rows for layer li + 1 (pkeep), at L + P rows per sequence with the
+    appended rows zero. Per layer: expand (P rows, not kept: cur becomes a free pair at L + P
+    rows, appended rows zero) -> current (the layer reads pairs[cur]) -> output (a pair that is
+    neither cur nor, under keep_input, the caller's: the layer writes its input gradient there
+    at L + P rows) -> take_replaced -> advance (no P: cur = output; inherited rows: zeroed, cur
+    = output at L + P rows; appended rows: rows [0, L) compacted into pairs[cur], which the
+    layer has consumed). q_of[i]: the fp8 image of pairs[i]'s 16-bit gradient while it is
+    current (ops.layernorm_bwd_fp8; dropped when prompt rows change it)."""
+
+    def __init__(self, dx, dxb, n_seq, L, Mmax, cdt, keep_input, main):
+        self.n_seq, self.L, self.Mmax, self.cdt = n_seq, L, Mmax, cdt
+        self.keep_input, self.main = keep_input, main
+        self.M, self.D = dx.shape
+        self.pairs = [(dx, dxb)]
+        for _ in range(2 if keep_input else 1):
+            self.pairs.append(self._pair())
+        self.cur, self.out, self.o, self.Lx = 0, None, None, L
+        self.q_mats, self.q_of = {}, {}
+
+    def _pair(self):
+        dx = self.pairs[0][0]
+        return (_empty((self.Mmax, self.D), dx.dtype, dx.device),
+                _empty((self.Mmax, self.D), self.cdt, dx.device))
+
+    def expand(self, P):
+        """The current gradient into a free pair at L + P rows per sequence, the P rows zero."""
+        n, L, Lx, D = self.n_seq, self.L, self.L + P, self.D
+        if len(self.pairs) == 2:
+            self.pairs.append(self._pair())
+        e = 2 if self.cur != 2 else 1
+        self.q_of.clear()
+        for src, dst in zip(self.pairs[self.cur], self.pairs[e]):
+            if src is not None:
+                v = dst[:n * Lx].view(n, Lx, D)
+                v[:, :L] = src[:self.M].view(n, L, D)
+                v[:, L:] = 0
+        self.cur = e
+
+    def current(self, Mx):
+        """(gradient, copy) w.r.t. the layer's output, its first Mx rows."""
+        return _rows(self.pairs[self.cur][0], Mx), _rows(self.pairs[self.cur][1], Mx)
+
+    def pop_q(self, Mx):
+        """The fp8 image of the current 16-bit gradient at Mx rows, if one is held."""
+        q = self.q_of.pop(self.cur, None)
+        return q if q is not None and q.rows == Mx else None
+
+    def output(self, P):
+        """Choose the pair the layer writes its input gradient to; its first n_seq * (L + P)
+        rows."""
+        Mx = self.n_seq * (self.L + P)
+        self.out = next(i for i in range(len(self.pairs)) if i != self.cur and (
+            i != 0 or (not self.keep_input and (P == 0 or self.pairs[0][0].shape[0] >= Mx))))
+        self.o = tuple(_rows(t, Mx) for t in self.pairs[self.out])
+        self.Lx = self.L + P
+        return self.o
+
+    def incoming(self, Mx):
+        """The caller's gradient buffer (all zero under last_rows), its first Mx rows."""
+        return self.pairs[0][0][:Mx]
+
+    def q_mat(self, Mx):
+        """Where ln_1's backward writes the fp8 image of the output pair."""
+        if self.out not in self.q_mats:
+            self.q_mats[self.out] = ops.Fp8Mat(self.Mmax, self.D, self.pairs[0][0].device)
+        return self.q_mats[self.out].narrow(Mx)
+
+    def set_q(self, q):
+        """The output pair's fp8 image (None: it has none)."""
+        if q is None:
+            self.q_of.pop(self.out, None)
+        else:
+            self.q_of[self.out] = q
+
+    def take_replaced(self, li, R, prompt_grads):
+        """Rows R = (row, count) the forward replaced: their gradient reported as
+        prompt_grads[('R', li)] and zeroed (it stops there)."""
+        if R is None:
+            return
+        r0, pr = R
+        views = [t.view(self.n_seq, self.Lx, self.D)[:, r0:r0 + pr]
+                 for t in self.o if t is not None]
+        if prompt_grads is not None:
+            prompt_grads[("R", li)] = views[0].clone()
+        for v in views:
+            v[:] = 0
+
+    def advance(self, li, P, inherit, ev, prompt_grads):
+        """The output pair becomes the next layer's current gradient; the P appended rows'
+        gradient is reported as prompt_grads[li]. ev: the side stream's reads of this layer."""
+        if not P:
+            self.cur = self.out
+            return
+        if ev is not None:
+            self.main.wait_event(ev)  # the side stream read the expanded gradient
+        n, L, Lx, D = self.n_seq, self.L, self.Lx, self.D
+        views = [None if t is None else t.view(n, Lx, D) for t in self.o]
+        if prompt_grads is not None:
+            prompt_grads[li] = views[0][:, L:].clone()
+        if inherit:
+            # these prompt rows replaced the previous layer's (dropped) ones: no gradient
+            # flows into them; the layout stays Lx for the previous layer
+            for v in views:
+                if v is not None:
+                    v[:, L:] = 0
+            self.cur = self.out
+        else:
+            # compact into the (consumed) expanded pair
+            for dst, v in zip(self.pairs[self.cur], views):
+                if v is not None:
+                    dst[:self.M].view(n, L, D).copy_(v[:, :L])
+
+    def result(self):
+        """(gradient, copy) w.r.t. the stack input."""
+        return self.pairs[self.cur][0][:self.M], _rows(self.pairs[self.cur][1], self.M)
+
+
+class _Backward:
+    """One BlockStack.backward call: gs the side stream of the PEFT weight-gradient reductions
+    (None: the current stream), gscale the half residual gradient's scale (None: none), grads
+    {param: f32 accumulator}, on_layer the caller's hook; backward adds its scratch buffers."""
+
+    def __init__(self, gs, gscale, grads, on_layer):
+        self.gs, self.gscale, self.grads, self.on_layer = gs, gscale, grads, on_layer
+
+    def side(self):
+        """Context for launching gradient reductions: the side stream (after the work that
+        produced their inputs on the current stream) or the current stream."""
+        if self.gs is None:
+            return nullcontext()
+        self.gs.wait_stream(torch.cuda.current_stream(self.gs.device))
+        return torch.cuda.stream(self.gs)
+
+    def grad(self, p):
+        g = self.grads.get(p)
+        if g is None:
+            raise KeyError("missing gradient buffer for a trainable parameter")
+        return g
+
+    def layer_done(self, li):
+        """Layer li's PEFT gradients are launched: the event after them on the side stream."""
+        ev = None
+        if self.gs is not None:
+            ev = torch.cuda.Event()
+            ev.record(self.gs)
+        if self.on_layer is not None:
+            self.on_layer(li)
+        return ev
+
+    def join(self):
+        """Make the current stream wait for the PEFT-gradient work on the side stream."""
+        if self.gs is not None:
+            torch.cuda.current_stream(self.gs.device).wait_stream(self.gs)
 
 
 class BlockStack:
@@ -89,7 +284,6 @@ class BlockStack:
         self.seed_dev = None
         self.precision = "bf16"  # 'bf16' | 'fp8' (QKV / c_fc / c_proj on the fp8 MFMA)
         self.dt = BF16  # 16-bit storage of activations, gradients and staged weights
-        self._gs = self._gscale = None  # backward()'s side stream and half-gradient scale
 
     def set_storage(self, dtype):
         """16-bit storage type of the stack: torch.bfloat16 (default) or torch.float16 (IEEE
@@ -264,6 +458,62 @@ class BlockStack:
         merges.append((B.detach(), None, None, 0.0, scratch, bt_pad[:r]))
         return old
 
+    # ------------------------------------------------------------------ prompt rows
+    # The reference runs a prompt layer as cat(x, prompts) -> block -> x[:, :L]
+    # (models/mvp_clip.py:158-175) and MaPLe overwrites rows [row, row + count) of x before a
+    # layer (models/maple_clip/model.py:352-395). Here, per layer (row_plan, Python ints only):
+    #   P        rows appended to every sequence: the layer runs at L + P rows and drops them
+    #   keep     the next layer appends the same count and replaces nothing: the rows stay and
+    #            that layer overwrites them (inherit there) — the same values without the
+    #            compact / expand copies. PROMPT_KEEP off, `stop` or a replacement ends a run
+    #   R        (row, count) overwritten in x first; at layer 0 in a copy, never in the
+    #            caller's input
+    # Forward: _rows_in before the block, _rows_out after it. Backward: _GradBufs walks the same
+    # plan upwards (the dropped rows carry zero gradient; an appended row's gradient is the
+    # prompt's, an inherited or replaced row's stops there).
+    @staticmethod
+    def row_plan(n_blocks, P_of, R_of, stop, keep):
+        """[_Rows] for layers [0, min(stop, n_blocks)): P_of {layer: appended rows}, R_of
+        {layer: (row, count) replaced}, keep: PROMPT_KEEP."""
+        n_run = n_blocks if stop is None else min(stop, n_blocks)
+        plan, carried = [], 0  # rows x carries from the previous layer (kept: same count here)
+        for idx in range(n_run):
+            P = P_of.get(idx, 0)
+            kept = bool(keep and P and idx + 1 < n_run and P_of.get(idx + 1, 0) == P
+                        and idx + 1 not in R_of)
+            plan.append(_Rows(P, bool(P) and carried == P, kept, R_of.get(idx)))
+            carried = P if kept else 0
+        return plan
+
+    @staticmethod
+    def _rows_in(x, p, idx, n_seq, L, prompts, replace):
+        """The layer's input at L + p.P rows per sequence."""
+        D, Lx = x.shape[1], L + p.P
+        if p.R is not None:
+            if idx == 0:
+                x = x.clone()  # never write into the caller's input
+            x.view(n_seq, -1, D)[:, p.R[0]:p.R[0] + p.R[1]] = replace[idx][1]
+        if p.inherit:
+            # the previous layer's prompt rows are dropped and this layer's appended in their
+            # place (models/mvp_clip.py:163-175: x[:N] then cat): overwrite them in x, which
+            # no saved tensor aliases (the previous layer saved its input, not its output)
+            x.view(n_seq, Lx, D)[:, L:] = prompts[idx]
+        elif p.P:
+            xe = _empty((n_seq * Lx, D), x.dtype, x.device)  # prompts cast to the stream's dtype
+            v = xe.view(n_seq, Lx, D)
+            v[:, :L] = x.view(n_seq, L, D)
+            v[:, L:] = prompts[idx]
+            x = xe
+        return x
+
+    @staticmethod
+    def _rows_out(x_out, p, n_seq, L):
+        """The layer's output as the next layer takes it: the appended rows kept or dropped."""
+        if not p.P or p.keep:
+            return x_out
+        D = x_out.shape[1]
+        return x_out.view(n_seq, L + p.P, D)[:, :L].reshape(n_seq * L, D)
+
     # ------------------------------------------------------------------ forward
     def forward(self, x, n_seq: int, L: int, save: bool, training: bool = False, prompts=None,
                 stop=None, replace=None, first_ln1=None, last_ln=None, last_rows=False):
@@ -290,194 +540,191 @@ class BlockStack:
         ops.attn_row_fwd, x_out and last_ln's y / mean / rstd are compact ([n_seq, D] / [n_seq]),
         and the adapter dropout draws the masks rows i * L had (ops.adapter_fwd(rows=...))."""
         self.stage()
-        M, D = x.shape
+        D = x.shape[1]
         xdt = x.dtype  # the residual stream's
-        H = self.n_head
         dev = x.device
         P_of = {int(i): int(t.shape[1]) for i, t in (prompts or {}).items()}
+        plan = self.row_plan(len(self.blocks), P_of, {i: (r0, pr.shape[-2]) for i, (r0, pr) in (
+            replace or {}).items()}, stop, self.PROMPT_KEEP)
         Mmax = n_seq * (L + max(P_of.values(), default=0))
-        tmp_h = _empty((Mmax, D), self.dt, dev)
-        q_g = ops.Fp8Mat(Mmax, 4 * D, dev) if self._fused_q8() else None
-        q_h = ops.Fp8Mat(Mmax, D, dev) if self._fused_q8(2) else None  # ln_1 / ln_2 out, fp8
-        tmp_g = _empty((Mmax, 4 * D), self.dt, dev) if q_g is None else None
-        tmp_pre = None if save else _empty((Mmax, 4 * D), self.dt, dev)
+        # the call's state, read by the two halves of a block (_fwd_attn, _fwd_mlp)
+        c = SimpleNamespace(n_seq=n_seq, L=L, save=save, training=training, plan=plan,
+                            e_resid=EPI_RESID16 if xdt == F16 else EPI_RESID)
+        c.tmp_h = _empty((Mmax, D), self.dt, dev)
+        c.q_g = ops.Fp8Mat(Mmax, 4 * D, dev) if self._fused_q8() else None
+        c.q_h = ops.Fp8Mat(Mmax, D, dev) if self._fused_q8(2) else None  # ln_1 / ln_2 out, fp8
+        c.tmp_g = _empty((Mmax, 4 * D), self.dt, dev) if c.q_g is None else None
+        c.tmp_pre = None if save else _empty((Mmax, 4 * D), self.dt, dev)
         saved = [] if save else None
         # bf16 adapter towers: each adapter runs fused with the LayerNorm that reads its output
-        # (ops.adapter_ln_fwd: ln_2 of the block, ln_1 of the next one); ln1_ready carries the
-        # statistics of an ln_1 the previous block already wrote into tmp_h
-        fuse_ln = (self.variant == "adapter" and q_h is None and D in (512, 768) and self.FUSE_LN)
+        # (ops.adapter_ln_fwd: ln_2 of the block, ln_1 of the next one, last_ln after the last);
+        # _fwd_mlp hands the next block's ln_1 (in tmp_h, with its statistics) to _fwd_attn
+        c.fuse_ln = self._fuse_ln(D)
         if xdt != F32 and not (self.variant == "vanilla" or (
-                q_g is None and q_h is None and not prompts and not replace and stop is None
-                and ((fuse_ln and last_ln is not None) or self.variant == "lora"))):
+                c.q_g is None and c.q_h is None and not prompts and not replace and stop is None
+                and ((c.fuse_ln and last_ln is not None) or self.variant == "lora"))):
             raise ValueError("a half residual stream runs the fused adapter tower (with its "
                              "closing LayerNorm fused: last_ln) or the LoRA tower, bf16, without "
                              "prompt rows, or the frozen (prompt) tower")
-        e_resid = EPI_RESID16 if xdt == F16 else EPI_RESID
-        ln1_ready = None
-        n_run = len(self.blocks) if stop is None else min(stop, len(self.blocks))
         if last_rows and not (self.rows_ok() and not prompts and not replace and stop is None):
             raise ValueError("last_rows: the bf16 adapter stack without prompt rows")
-        carried = 0  # prompt rows x carries from the previous layer (kept: same count here)
-        for idx, (blk, st) in enumerate(zip(self.blocks, self.staged)):
-            if stop is not None and idx >= stop:
-                break
-            if replace and idx in replace:
-                r0, pr = replace[idx]
-                if idx == 0:
-                    x = x.clone()  # never write into the caller's input
-                x.view(n_seq, -1, D)[:, r0:r0 + pr.shape[-2]] = pr
-            P = P_of.get(idx, 0)
-            Lx = L + P
-            Mx = n_seq * Lx
-            inherit = bool(P) and carried == P
-            if inherit:
-                # the previous layer's prompt rows are dropped and this layer's appended in their
-                # place (models/mvp_clip.py:163-175: x[:N] then cat): overwrite them in x, which
-                # no saved tensor aliases (the previous layer saved its input, not its output)
-                x.view(n_seq, Lx, D)[:, L:] = prompts[idx]
-            elif P:
-                xe = _empty((Mx, D), xdt, dev)  # prompt rows cast to the stream's dtype
-                v = xe.view(n_seq, Lx, D)
-                v[:, :L] = x.view(n_seq, L, D)
-                v[:, L:] = prompts[idx]
-                x = xe
-            th = tmp_h[:Mx]
-            s = {}
-            mean1 = _empty((Mx,), F32, dev)
-            rstd1 = _empty((Mx,), F32, dev)
-            h1 = _empty((Mx, D), self.dt, dev) if (save and self.variant == "lora") else th
-            qkv = _empty((Mx, 3 * D), self.dt, dev)
-            if q_h is not None:  # bf16 h1 only when LoRA's gradient reads it
-                qa = ops.layernorm_fwd_fp8(x, blk.ln_1.weight, blk.ln_1.bias, q_h.narrow(Mx),
-                                           mean1, rstd1, y=None if h1 is th else h1)
-                ops.gemm_nt_fp8(qa, st.q["wqkv"], EPI_BF16, qkv, bias=blk.attn.in_proj_bias)
-            else:
-                if ln1_ready is not None:  # written by the previous block's fused adapter
-                    mean1, rstd1 = ln1_ready
-                elif (idx == 0 and first_ln1 is not None and P == 0
-                      and not (replace and 0 in replace)):
-                    h1, mean1, rstd1 = first_ln1
-                else:
-                    ops.layernorm_fwd(x, blk.ln_1.weight, blk.ln_1.bias, h1, mean1, rstd1)
-                self._gemm(st, "wqkv", h1, EPI_BF16, qkv, bias=blk.attn.in_proj_bias)
-            ln1_ready = None
-            # rows of the row-wise part: all of them, or (last_rows, last block) row 0 of every
-            # sequence — xr their residual input, rid their dropout row ids
-            rows = last_rows and idx == len(self.blocks) - 1
-            Mr, xr, rid = Mx, x, None
-            if rows:
-                Mr, rid = n_seq, (Lx, 0)
-                xr = _empty((Mr, D), xdt, dev)
-                xr.copy_(x.view(n_seq, Lx, D)[:, 0])
-                th = tmp_h[:Mr]
-                O = _empty((Mr, D), self.dt, dev)
-                lse = _empty((n_seq * H,), F32, dev)
-                ops.attn_row_fwd(qkv, O, lse, n_seq, Lx, H, 0, self.causal)
-            else:
-                O = _empty((Mx, D), self.dt, dev)
-                lse = _empty((n_seq * H, Lx), F32, dev)
-                ops.attn_fwd(qkv, O, lse, n_seq, Lx, H, self.causal)
-            x_mid = _empty((Mr, D), xdt, dev)
-            if self.variant == "adapter":
-                ad = blk.adaptmlp
-                keep = 1.0 - ad.dropout if (training and ad.dropout > 0) else 1.0
-                seed1 = next(_seed_counter) * 0x9E3779B1
-                z1 = _empty((Mr, D), self.dt, dev)
-                ops.gemm_nt(O, st.wo, EPI_BF16, z1, bias=blk.attn.out_proj.bias)
-                hd1 = _empty((Mr, ad.down_size), self.dt, dev)
-                mean2 = _empty((Mr,), F32, dev)
-                rstd2 = _empty((Mr,), F32, dev)
-                if fuse_ln and q_g is None:
-                    ops.adapter_ln_fwd(z1, st.wd, ad.down_proj.bias, st.wu, ad.up_proj.bias,
-                                       ad.scale, keep, seed1, xr, x_mid, hd1, blk.ln_2.weight,
-                                       blk.ln_2.bias, th, mean2, rstd2, seed_dev=self.seed_dev,
-                                       rows=rid)
-                    ln2_done = True
-                else:
-                    ops.adapter_fwd(z1, st.wd, ad.down_proj.bias, st.wu, ad.up_proj.bias, ad.scale,
-                                    keep, seed1, xr, x_mid, hd1, seed_dev=self.seed_dev, rows=rid)
-                    ln2_done = False
-                s.update(z1=z1, hd1=hd1, keep=keep)
-            else:
-                ops.gemm_nt(O, st.wo, e_resid, x_mid, bias=blk.attn.out_proj.bias, aux=x)
-                mean2 = _empty((Mx,), F32, dev)
-                rstd2 = _empty((Mx,), F32, dev)
-                ln2_done = False
-            pre = _empty((Mr, 4 * D), self.dt, dev) if save else tmp_pre[:Mr]
-            # training saves QuickGELU'(pre) (the c_fc dX epilogue is then a plain multiply)
-            if q_g is not None:
-                # ln_2 and QuickGELU(pre) only as the fp8 operands of c_fc / c_proj (inference
-                # discards QuickGELU')
-                if q_h is not None:
-                    qa = ops.layernorm_fwd_fp8(x_mid, blk.ln_2.weight, blk.ln_2.bias,
-                                               q_h.narrow(Mx), mean2, rstd2)
-                else:
-                    ops.layernorm_fwd(x_mid, blk.ln_2.weight, blk.ln_2.bias, th, mean2, rstd2)
-                    qa = ops.quant_fp8(th)
-                g_in = ops.gemm_nt_fp8(qa, st.q["wfc"], EPI_GELU_D_Q8, pre,
-                                       bias=blk.mlp.c_fc.bias, q_out=q_g.narrow(Mx))
-                wpr = lambda epi, out0, **kw: ops.gemm_nt_fp8(g_in, st.q["wpr"], epi, out0, **kw)  # noqa: E731
-            else:
-                if not ln2_done:
-                    ops.layernorm_fwd(x_mid, blk.ln_2.weight, blk.ln_2.bias, th, mean2, rstd2)
-                self._gemm(st, "wfc", th, EPI_GELU_D if save else EPI_GELU, pre,
-                           bias=blk.mlp.c_fc.bias, out1=tmp_g[:Mr])
-                wpr = lambda epi, out0, **kw: (  # noqa: E731
-                    self._gemm_rows(st, "wpr", tmp_g, epi, out0, n_seq, Lx, **kw) if rows
-                    else self._gemm(st, "wpr", tmp_g[:Mr], epi, out0, **kw))
-            x_out = _empty((Mr, D), xdt, dev)
-            if self.variant == "adapter":
-                ad = blk.adaptmlp
-                seed2 = next(_seed_counter) * 0x9E3779B1
-                z2 = _empty((Mr, D), self.dt, dev)
-                wpr(EPI_BF16, z2, bias=blk.mlp.c_proj.bias)
-                hd2 = _empty((Mr, ad.down_size), self.dt, dev)
-                nxt = idx + 1
-                if (fuse_ln and nxt < len(self.blocks) and (stop is None or nxt < stop)
-                        and not P_of.get(nxt, 0) and not P and not (replace and nxt in replace)):
-                    # the next block's ln_1 into tmp_h (c_fc has consumed it by now: same stream)
-                    nb = self.blocks[nxt]
-                    m1 = _empty((Mx,), F32, dev)
-                    r1 = _empty((Mx,), F32, dev)
-                    ops.adapter_ln_fwd(z2, st.wd, ad.down_proj.bias, st.wu, ad.up_proj.bias,
-                                       ad.scale, s["keep"], seed2, x_mid, x_out, hd2,
-                                       nb.ln_1.weight, nb.ln_1.bias, th, m1, r1,
-                                       seed_dev=self.seed_dev)
-                    ln1_ready = (m1, r1)
-                elif (last_ln is not None and fuse_ln and nxt == len(self.blocks) and not P
-                      and stop is None):
-                    # the LayerNorm after the stack (ln_post) over every row (last_rows: over
-                    # the rows the block still has)
-                    ops.adapter_ln_fwd(z2, st.wd, ad.down_proj.bias, st.wu, ad.up_proj.bias,
-                                       ad.scale, s["keep"], seed2, x_mid, x_out, hd2,
-                                       last_ln["w"], last_ln["b"], last_ln["y"], last_ln["mean"],
-                                       last_ln["rstd"], seed_dev=self.seed_dev, rows=rid)
-                    last_ln["done"] = True
-                else:
-                    ops.adapter_fwd(z2, st.wd, ad.down_proj.bias, st.wu, ad.up_proj.bias, ad.scale,
-                                    s["keep"], seed2, x_mid, x_out, hd2, seed_dev=self.seed_dev,
-                                    rows=rid)
-                s.update(z2=z2, hd2=hd2)
-            else:
-                wpr(e_resid, x_out, bias=blk.mlp.c_proj.bias, aux=x_mid)
-            # a run of prompt layers with one prompt count keeps the rows between them (no
-            # compact-and-expand copies): the next layer overwrites them
-            pkeep = (self.PROMPT_KEEP and bool(P) and idx + 1 < n_run
-                     and P_of.get(idx + 1, 0) == P and not (replace and idx + 1 in replace))
+        c.last_ln = last_ln if (last_ln is not None
+                                and self.last_ln_fused(D, prompts, stop)) else None
+        ln1 = first_ln1 if plan and plan[0].plain else None
+        for idx, p in enumerate(plan):
+            s = SavedLayer(p, rows=last_rows and idx == len(self.blocks) - 1)
+            x = self._rows_in(x, p, idx, n_seq, L, prompts, replace)
+            ln2_done = self._fwd_attn(c, idx, s, x, ln1)
+            x_out, ln1 = self._fwd_mlp(c, idx, s, ln2_done)
             if save:
-                s.update(x_in=x, mean1=mean1, rstd1=rstd1, qkv=qkv, O=O, lse=lse, x_mid=x_mid,
-                         mean2=mean2, rstd2=rstd2, gd=pre, P=P, pkeep=pkeep, inherit=inherit,
-                         rows=rows)
-                if replace and idx in replace:
-                    s["R"] = (replace[idx][0], replace[idx][1].shape[-2])
-                if self.variant == "lora":
-                    s["h1"] = h1
                 saved.append(s)
-            if not P or pkeep:
-                x, carried = x_out, (P if pkeep else 0)
-            else:
-                x, carried = x_out.view(n_seq, Lx, D)[:, :L].reshape(n_seq * L, D), 0
+            x = self._rows_out(x_out, p, n_seq, L)
         return x, saved
+
+    def _fuse_ln(self, D):
+        return (self.variant == "adapter" and not self._fused_q8(2) and D in (512, 768)
+                and self.FUSE_LN)
+
+    def last_ln_fused(self, D, prompts=None, stop=None):
+        """forward(last_ln=...) at width D writes last_ln's y / mean / rstd (the LayerNorm after
+        the stack fused into the last block's second adapter): the callers' test for reading
+        them instead of running that LayerNorm."""
+        last = len(self.blocks) - 1
+        return (self._fuse_ln(D) and stop is None and last >= 0 and not any(
+            int(i) == last and t.shape[1] for i, t in (prompts or {}).items()))
+
+    def _fwd_attn(self, c, idx, s, x, ln1):
+        """x_mid = x + [A](out_proj(attn(ln_1(x)))), fused with ln_2 where the adapter is
+        (returns whether: tmp_h then holds ln_2(x_mid)). ln1: (ln_1(x), mean, rstd) already
+        computed (bf16 operands), or None."""
+        blk, st = self.blocks[idx], self.staged[idx]
+        n_seq, H, dev, xdt, D = c.n_seq, self.n_head, x.device, x.dtype, x.shape[1]
+        Lx = c.L + s.P
+        Mx = n_seq * Lx
+        th = c.tmp_h[:Mx]
+        mean1 = _empty((Mx,), F32, dev)
+        rstd1 = _empty((Mx,), F32, dev)
+        h1 = _empty((Mx, D), self.dt, dev) if (c.save and self.variant == "lora") else th
+        qkv = _empty((Mx, 3 * D), self.dt, dev)
+        if c.q_h is not None:  # bf16 h1 only when LoRA's gradient reads it
+            qa = ops.layernorm_fwd_fp8(x, blk.ln_1.weight, blk.ln_1.bias, c.q_h.narrow(Mx),
+                                       mean1, rstd1, y=None if h1 is th else h1)
+            ops.gemm_nt_fp8(qa, st.q["wqkv"], EPI_BF16, qkv, bias=blk.attn.in_proj_bias)
+        else:
+            if ln1 is not None:
+                h1, mean1, rstd1 = ln1
+            else:
+                ops.layernorm_fwd(x, blk.ln_1.weight, blk.ln_1.bias, h1, mean1, rstd1)
+            self._gemm(st, "wqkv", h1, EPI_BF16, qkv, bias=blk.attn.in_proj_bias)
+        # rows of the row-wise part: all of them, or (last_rows, last block) row 0 of every
+        # sequence — xr their residual input, rid their dropout row ids
+        Mr, xr, rid = Mx, x, None
+        if s.rows:
+            Mr, rid = n_seq, (Lx, 0)
+            xr = _empty((Mr, D), xdt, dev)
+            xr.copy_(x.view(n_seq, Lx, D)[:, 0])
+            th = c.tmp_h[:Mr]
+            O = _empty((Mr, D), self.dt, dev)
+            lse = _empty((n_seq * H,), F32, dev)
+            ops.attn_row_fwd(qkv, O, lse, n_seq, Lx, H, 0, self.causal)
+        else:
+            O = _empty((Mx, D), self.dt, dev)
+            lse = _empty((n_seq * H, Lx), F32, dev)
+            ops.attn_fwd(qkv, O, lse, n_seq, Lx, H, self.causal)
+        x_mid = _empty((Mr, D), xdt, dev)
+        ln2_done = False
+        if self.variant == "adapter":
+            ad = blk.adaptmlp
+            s.keep = 1.0 - ad.dropout if (c.training and ad.dropout > 0) else 1.0
+            seed1 = next(_seed_counter) * 0x9E3779B1
+            s.z1 = _empty((Mr, D), self.dt, dev)
+            ops.gemm_nt(O, st.wo, EPI_BF16, s.z1, bias=blk.attn.out_proj.bias)
+            s.hd1 = _empty((Mr, ad.down_size), self.dt, dev)
+            s.mean2 = _empty((Mr,), F32, dev)
+            s.rstd2 = _empty((Mr,), F32, dev)
+            if c.fuse_ln and c.q_g is None:
+                ops.adapter_ln_fwd(s.z1, st.wd, ad.down_proj.bias, st.wu, ad.up_proj.bias,
+                                   ad.scale, s.keep, seed1, xr, x_mid, s.hd1, blk.ln_2.weight,
+                                   blk.ln_2.bias, th, s.mean2, s.rstd2, seed_dev=self.seed_dev,
+                                   rows=rid)
+                ln2_done = True
+            else:
+                ops.adapter_fwd(s.z1, st.wd, ad.down_proj.bias, st.wu, ad.up_proj.bias, ad.scale,
+                                s.keep, seed1, xr, x_mid, s.hd1, seed_dev=self.seed_dev, rows=rid)
+        else:
+            ops.gemm_nt(O, st.wo, c.e_resid, x_mid, bias=blk.attn.out_proj.bias, aux=x)
+            s.mean2 = _empty((Mx,), F32, dev)
+            s.rstd2 = _empty((Mx,), F32, dev)
+        s.x_in, s.mean1, s.rstd1, s.qkv, s.O, s.lse, s.x_mid = x, mean1, rstd1, qkv, O, lse, x_mid
+        if self.variant == "lora":
+            s.h1 = h1
+        return ln2_done
+
+    def _fwd_mlp(self, c, idx, s, ln2_done):
+        """x_out = x_mid + [A](c_proj(gelu(c_fc(ln_2(x_mid))))), fused where the adapter is with
+        the LayerNorm that reads x_out. Returns (x_out, the next block's (ln_1(x_out), mean,
+        rstd) or None)."""
+        blk, st = self.blocks[idx], self.staged[idx]
+        x_mid, n_seq, save = s.x_mid, c.n_seq, c.save
+        dev, xdt, D = x_mid.device, x_mid.dtype, x_mid.shape[1]
+        Lx = c.L + s.P
+        Mx = n_seq * Lx
+        Mr, rid = (n_seq, (Lx, 0)) if s.rows else (Mx, None)
+        th = c.tmp_h[:Mr]
+        pre = _empty((Mr, 4 * D), self.dt, dev) if save else c.tmp_pre[:Mr]
+        # training saves QuickGELU'(pre) (the c_fc dX epilogue is then a plain multiply)
+        if c.q_g is not None:
+            # ln_2 and QuickGELU(pre) only as the fp8 operands of c_fc / c_proj (inference
+            # discards QuickGELU')
+            if c.q_h is not None:
+                qa = ops.layernorm_fwd_fp8(x_mid, blk.ln_2.weight, blk.ln_2.bias,
+                                           c.q_h.narrow(Mx), s.mean2, s.rstd2)
+            else:
+                ops.layernorm_fwd(x_mid, blk.ln_2.weight, blk.ln_2.bias, th, s.mean2, s.rstd2)
+                qa = ops.quant_fp8(th)
+            g_in = ops.gemm_nt_fp8(qa, st.q["wfc"], EPI_GELU_D_Q8, pre,
+                                   bias=blk.mlp.c_fc.bias, q_out=c.q_g.narrow(Mx))
+            wpr = lambda epi, out0, **kw: ops.gemm_nt_fp8(g_in, st.q["wpr"], epi, out0, **kw)  # noqa: E731
+        else:
+            if not ln2_done:
+                ops.layernorm_fwd(x_mid, blk.ln_2.weight, blk.ln_2.bias, th, s.mean2, s.rstd2)
+            self._gemm(st, "wfc", th, EPI_GELU_D if save else EPI_GELU, pre,
+                       bias=blk.mlp.c_fc.bias, out1=c.tmp_g[:Mr])
+            wpr = lambda epi, out0, **kw: (  # noqa: E731
+                self._gemm_rows(st, "wpr", c.tmp_g, epi, out0, n_seq, Lx, **kw) if s.rows
+                else self._gemm(st, "wpr", c.tmp_g[:Mr], epi, out0, **kw))
+        s.gd = pre
+        x_out = _empty((Mr, D), xdt, dev)
+        if self.variant != "adapter":
+            wpr(c.e_resid, x_out, bias=blk.mlp.c_proj.bias, aux=x_mid)
+            return x_out, None
+        ad = blk.adaptmlp
+        seed2 = next(_seed_counter) * 0x9E3779B1
+        s.z2 = _empty((Mr, D), self.dt, dev)
+        wpr(EPI_BF16, s.z2, bias=blk.mlp.c_proj.bias)
+        s.hd2 = _empty((Mr, ad.down_size), self.dt, dev)
+        nxt, ln1 = idx + 1, None
+        if c.fuse_ln and nxt < len(c.plan) and not s.P and c.plan[nxt].plain:
+            # the next block's ln_1 into tmp_h (c_fc has consumed it by now: same stream)
+            nb = self.blocks[nxt]
+            ln1 = (th, _empty((Mx,), F32, dev), _empty((Mx,), F32, dev))
+            ops.adapter_ln_fwd(s.z2, st.wd, ad.down_proj.bias, st.wu, ad.up_proj.bias,
+                               ad.scale, s.keep, seed2, x_mid, x_out, s.hd2,
+                               nb.ln_1.weight, nb.ln_1.bias, *ln1, seed_dev=self.seed_dev)
+        elif c.last_ln is not None and nxt == len(self.blocks):
+            # the LayerNorm after the stack (ln_post) over every row (last_rows: over
+            # the rows the block still has)
+            ll = c.last_ln
+            ops.adapter_ln_fwd(s.z2, st.wd, ad.down_proj.bias, st.wu, ad.up_proj.bias,
+                               ad.scale, s.keep, seed2, x_mid, x_out, s.hd2,
+                               ll["w"], ll["b"], ll["y"], ll["mean"], ll["rstd"],
+                               seed_dev=self.seed_dev, rows=rid)
+        else:
+            ops.adapter_fwd(s.z2, st.wd, ad.down_proj.bias, st.wu, ad.up_proj.bias, ad.scale,
+                            s.keep, seed2, x_mid, x_out, s.hd2, seed_dev=self.seed_dev,
+                            rows=rid)
+        return x_out, ln1
+
 
     # ------------------------------------------------------------------ backward
     def backward(self, saved, dx, dxb, grads, n_seq: int, L: int, on_layer=None,
@@ -490,7 +737,7 @@ class BlockStack:
         grad_stream: optional side HIP stream for the PEFT weight-gradient reductions (adapter
         dW/db, LoRA dA/dB), which feed only `grads`: they run beside the dX chain's MFMA-bound
         GEMMs. Each layer waits for the previous layer's side work before rewriting the shared
-        gradient buffers the side reads; sync_grads() joins it (done before returning).
+        gradient buffers the side reads; the current stream joins it before returning.
 
         need_dx=False (a tower whose input is frozen: patch / token embeddings): nothing below
         layer 0's first trainable parameter needs a gradient, so its out-proj dX, attention
@@ -524,217 +771,155 @@ class BlockStack:
         M, D = dx.shape
         gdt = dx.dtype
         if gdt != F32 and (gscale is None or prompt_grads is not None
-                           or any(s.get("P", 0) or "R" in s for s in saved)):
+                           or any(s.P or s.R is not None for s in saved)):
             raise ValueError("a half residual gradient needs its gscale and no prompt rows")
-        self._gscale = gscale
+        c = _Backward(grad_stream, gscale, grads, on_layer)
+        c.n_seq, c.L = n_seq, L
         # the half gradient's consumers read it directly: no bf16 copies (LayerNorm backward
         # writes the half gradient only)
-        nocopy = gdt != F32 and self.half_grad_direct()
+        c.nocopy = nocopy = gdt != F32 and self.half_grad_direct()
         cdt = None if nocopy else self.dt  # the copies' type (None: not kept)
-        main = torch.cuda.current_stream(dx.device)
-        self._gs = grad_stream
-        ev = None
-        H = self.n_head
         dev = dx.device
-        Mmax = n_seq * (L + max((s.get("P", 0) for s in saved), default=0))
-        q_da = ops.Fp8Mat(Mmax, 4 * D, dev) if self._fused_q8() else None
+        Mmax = n_seq * (L + max((s.P for s in saved), default=0))
+        c.q_da = ops.Fp8Mat(Mmax, 4 * D, dev) if self._fused_q8() else None
         # the attention backward's dq|dk|dv as the fp8 QKV dX operand (LoRA reads them in bf16)
         fuse_attn = self._fused_q8(3) and self.variant != "lora" and Mmax // n_seq <= 224
-        q_dqkv = ops.Fp8Mat(Mmax, 3 * D, dev) if fuse_attn else None
-        da = _empty((Mmax, 4 * D), self.dt, dev) if q_da is None else None
-        dh = _empty((Mmax, D), self.dt, dev)
-        dO = _empty((Mmax, D), self.dt, dev)
-        dqkv = _empty((Mmax, 3 * D), self.dt, dev)
-        dz = _empty((Mmax, D), self.dt, dev) if self.variant == "adapter" else None
-        dx_mid = _empty((Mmax, D), gdt, dev)
-        dx_midb = _empty((Mmax, D), cdt, dev)
+        c.q_dqkv = ops.Fp8Mat(Mmax, 3 * D, dev) if fuse_attn else None
+        c.da = _empty((Mmax, 4 * D), self.dt, dev) if c.q_da is None else None
+        c.dh = _empty((Mmax, D), self.dt, dev)
+        c.dO = _empty((Mmax, D), self.dt, dev)
+        c.dqkv = _empty((Mmax, 3 * D), self.dt, dev)
+        c.dz = _empty((Mmax, D), self.dt, dev) if self.variant == "adapter" else None
+        c.dx_mid = _empty((Mmax, D), gdt, dev)
+        c.dx_midb = _empty((Mmax, D), cdt, dev)
         # output-gradient buffers: the incoming pair and one more (ping-pong); prompt layers
         # expand the current gradient into a free pair and compact their output back
-        pairs = [(dx, None if nocopy else dxb),
-                 (_empty((Mmax, D), gdt, dev), _empty((Mmax, D), cdt, dev))]
-        if keep_input:
-            pairs.append((_empty((Mmax, D), gdt, dev), _empty((Mmax, D), cdt, dev)))
-        cur = 0
+        bufs = _GradBufs(dx, None if nocopy else dxb, n_seq, L, Mmax, cdt, keep_input,
+                         torch.cuda.current_stream(dev))
         # fp8 (no adapter: the block output gradient feeds c_proj dX directly): ln_1's backward
         # also writes its result as the fp8 operand of the next (lower) block's c_proj dX GEMM
-        # (ops.layernorm_bwd_fp8), so that block skips quant_fp8. q_of[i]: the fp8 image of
-        # pairs[i]'s bf16 gradient while it is current (dropped when prompt rows change it).
-        fuse_ln_q = self._fused_q8(4) and self.variant != "adapter" and D % 256 == 0
-        q_mats, q_of = {}, {}
+        # (ops.layernorm_bwd_fp8), so that block skips quant_fp8 (_GradBufs.q_of)
+        c.fuse_ln_q = self._fused_q8(4) and self.variant != "adapter" and D % 256 == 0
+        ev = None
         for li in range(len(self.blocks) - 1, -1, -1):
-            blk, st, s = self.blocks[li], self.staged[li], saved[li]
+            s = saved[li]
             if ev is not None:
-                main.wait_event(ev)  # side reads of the buffers this layer rewrites are done
-            P = s.get("P", 0)
-            Lx = L + P
-            Mx = n_seq * Lx
-            if P and len(pairs) == 2:
-                pairs.append((_empty((Mmax, D), F32, dev), _empty((Mmax, D), self.dt, dev)))
-            if P and not s.get("pkeep"):  # (kept rows: the gradient is already in the Lx layout)
-                e = 2 if cur != 2 else 1
-                q_of.clear()
-                for src, dst in zip(pairs[cur], pairs[e]):
-                    v = dst[:Mx].view(n_seq, Lx, D)
-                    v[:, :L] = src[:M].view(n_seq, L, D)
-                    v[:, L:] = 0
-                cur = e
-            gx, gxb = _rows(pairs[cur][0], Mx), _rows(pairs[cur][1], Mx)
-            rows = bool(s.get("rows"))
-            if rows != (last_rows is not None and li == len(self.blocks) - 1):
+                bufs.main.wait_event(ev)  # side reads of the buffers this layer rewrites are done
+            Mx = n_seq * (L + s.P)
+            if s.P and not s.pkeep:  # (kept rows: the gradient is already in the Lx layout)
+                bufs.expand(s.P)
+            gx, gxb = bufs.current(Mx)
+            if bool(s.rows) != (last_rows is not None and li == len(self.blocks) - 1):
                 raise ValueError("last_rows: the forward's compact last block and its gradient")
-            Mr = Mx
-            if rows:
-                Mr = n_seq
+            if s.rows:
                 gx, gxb = last_rows
-            out = next(i for i in range(len(pairs)) if i != cur and (
-                i != 0 or (not keep_input and (P == 0 or pairs[0][0].shape[0] >= Mx))))
-            ox, oxb = _rows(pairs[out][0], Mx), _rows(pairs[out][1], Mx)
-            # ---- MLP sub-block: x_out = x_mid + [A](c_proj(gelu(c_fc(ln_2(x_mid)))))
-            if self.variant == "adapter":
-                dY = self._adapter_bwd(blk, st, gx if nocopy else gxb, s["hd2"], s["z2"],
-                                       s["keep"], dz[:Mr], grads, pad=(n_seq, Lx) if rows else None)
-            else:
-                dY = gxb
-            if q_da is not None:
-                qdy = q_of.pop(cur, None) if self.variant != "adapter" else None
-                qdy = qdy if qdy is not None and qdy.rows == Mx else ops.quant_fp8(dY)
-                q = ops.gemm_nt_fp8(qdy, st.q["wprT"], EPI_MUL_Q8, None, aux=s["gd"],
-                                    q_out=q_da.narrow(Mx))
-                ops.gemm_nt_fp8(q, st.q["wfcT"], EPI_BF16, dh[:Mx])
-            else:
-                self._gemm(st, "wprT", dY, EPI_MUL, da[:Mr], aux=s["gd"])
-                if rows:
-                    self._gemm_rows(st, "wfcT", da, EPI_BF16, dh[:Mr], n_seq, Lx, scratch=dh)
-                else:
-                    self._gemm(st, "wfcT", da[:Mr], EPI_BF16, dh[:Mr])
-            ops.layernorm_bwd(dh[:Mr], s["x_mid"], s["mean2"], s["rstd2"], blk.ln_2.weight,
-                              dx_mid[:Mr], _rows(dx_midb, Mr), dres=gx)
-            # ---- attention sub-block: x_mid = x_in + [A](out_proj(attn(ln_1(x_in))))
-            first = li == 0 and not need_dx
-            if self.variant == "adapter":
-                dY = self._adapter_bwd(blk, st, dx_mid[:Mr] if nocopy else dx_midb[:Mr],
-                                       s["hd1"], s["z1"], s["keep"], None if first else dz[:Mr],
-                                       grads, pad=(n_seq, Lx) if rows else None)
-            else:
-                dY = dx_midb[:Mx]
-            if first and self.variant != "lora":
-                self._layer_done(li, grad_stream, on_layer)
+            ox, oxb = bufs.output(s.P)
+            self._bwd_mlp(c, li, s, gx, gxb, bufs.pop_q(Mx))
+            more = self._bwd_attn(c, li, s, ox, oxb, bufs, first=li == 0 and not need_dx)
+            ev = c.layer_done(li)
+            if not more:
                 break
-            ops.gemm_nt(dY, st.woT, EPI_BF16, dO[:Mr])
-            attn = blk.attn
-            if self.variant == "lora":
-                self._lora_grad(dY, s["O"], attn.out_proj.lora_A, attn.out_proj.lora_B,
-                                attn.scaling, grads, st.lora_out)
-            if rows:  # (da and dh are free: the MLP chain is done, QKV dX rewrites dh below)
-                qd = self._attn_bwd_rows(s, dO[:Mr], dqkv[:Mx], n_seq, Lx, da, dh)
-            elif q_dqkv is not None and not first:
-                qd = ops.attn_bwd_fp8(s["qkv"], s["O"], dO[:Mx], s["lse"], q_dqkv.narrow(Mx), n_seq,
-                                      Lx, H, self.causal)
-            else:
-                qd = None
-                ops.attn_bwd(s["qkv"], s["O"], dO[:Mx], s["lse"], dqkv[:Mx], n_seq, Lx, H,
-                             self.causal)
-            if self.variant == "lora":
-                self._lora_grad(dqkv[:Mx], s["h1"], attn.in_proj_weight_lora_A,
-                                attn.in_proj_weight_lora_B, attn.scaling, grads, st.lora_in)
-            if first:
-                self._layer_done(li, grad_stream, on_layer)
-                break
-            if qd is not None:
-                ops.gemm_nt_fp8(qd, st.q["wqkvT"], EPI_BF16, dh[:Mx])
-            else:
-                self._gemm(st, "wqkvT", dqkv[:Mx], EPI_BF16, dh[:Mx])
-            dres1 = dx_mid[:Mx]
-            if rows:
-                # into the caller's zero buffer (never an output buffer: keep_input)
-                dres1 = self._spread(dx_mid[:Mr], n_seq, Lx, dst=pairs[0][0][:Mx], fill=None)
-            if fuse_ln_q and "R" not in s and not P:
-                if out not in q_mats:
-                    q_mats[out] = ops.Fp8Mat(Mmax, D, dev)
-                q_of[out] = ops.layernorm_bwd_fp8(dh[:Mx], s["x_in"], s["mean1"], s["rstd1"],
-                                                  blk.ln_1.weight, ox, oxb, q_mats[out].narrow(Mx),
-                                                  dres=dx_mid[:Mx])
-            else:
-                q_of.pop(out, None)
-                ops.layernorm_bwd(dh[:Mx], s["x_in"], s["mean1"], s["rstd1"], blk.ln_1.weight, ox,
-                                  oxb, dres=dres1)
-            ev = self._layer_done(li, grad_stream, on_layer)
-            if "R" in s:
-                r0, pr = s["R"]
-                if prompt_grads is not None:
-                    prompt_grads[("R", li)] = ox.view(n_seq, Lx, D)[:, r0:r0 + pr].clone()
-                ox.view(n_seq, Lx, D)[:, r0:r0 + pr] = 0
-                oxb.view(n_seq, Lx, D)[:, r0:r0 + pr] = 0
-            if P:
-                if ev is not None:
-                    main.wait_event(ev)  # the side stream read the expanded gradient
-                v = ox.view(n_seq, Lx, D)
-                if prompt_grads is not None:
-                    prompt_grads[li] = v[:, L:].clone()
-                if s.get("inherit"):
-                    # these prompt rows replaced the previous layer's (dropped) ones: no gradient
-                    # flows into them; the layout stays Lx for the previous layer
-                    v[:, L:] = 0
-                    oxb.view(n_seq, Lx, D)[:, L:] = 0
-                    cur = out
-                else:
-                    # compact into the (consumed) expanded pair
-                    pairs[cur][0][:M].view(n_seq, L, D).copy_(v[:, :L])
-                    pairs[cur][1][:M].view(n_seq, L, D).copy_(oxb.view(n_seq, Lx, D)[:, :L])
-            else:
-                cur = out
-        self.sync_grads()
-        self._gscale = None
+            bufs.take_replaced(li, s.R, prompt_grads)
+            bufs.advance(li, s.P, s.inherit, ev, prompt_grads)
+        c.join()
         if not need_dx:
             return None, None
-        return pairs[cur][0][:M], _rows(pairs[cur][1], M)
+        return bufs.result()
 
-    @staticmethod
-    def _layer_done(li, grad_stream, on_layer):
-        ev = None
-        if grad_stream is not None:
-            ev = torch.cuda.Event()
-            ev.record(grad_stream)
-        if on_layer is not None:
-            on_layer(li)
-        return ev
+    def _bwd_mlp(self, c, li, s, gx, gxb, qdy):
+        """Backward of x_out = x_mid + [A](c_proj(gelu(c_fc(ln_2(x_mid))))): (gx, gxb) the
+        gradient w.r.t. x_out and its copy, qdy its fp8 image or None; writes c.dx_mid /
+        c.dx_midb, the gradient w.r.t. x_mid."""
+        blk, st = self.blocks[li], self.staged[li]
+        n_seq, Lx = c.n_seq, c.L + s.P
+        Mx = n_seq * Lx
+        Mr = n_seq if s.rows else Mx
+        if self.variant == "adapter":
+            dY = self._adapter_bwd(c, blk, st, gx if c.nocopy else gxb, s.hd2, s.z2, s.keep,
+                                   c.dz[:Mr], pad=(n_seq, Lx) if s.rows else None)
+        else:
+            dY = gxb
+        if c.q_da is not None:
+            if qdy is None:
+                qdy = ops.quant_fp8(dY)
+            q = ops.gemm_nt_fp8(qdy, st.q["wprT"], EPI_MUL_Q8, None, aux=s.gd,
+                                q_out=c.q_da.narrow(Mx))
+            ops.gemm_nt_fp8(q, st.q["wfcT"], EPI_BF16, c.dh[:Mx])
+        else:
+            self._gemm(st, "wprT", dY, EPI_MUL, c.da[:Mr], aux=s.gd)
+            if s.rows:
+                self._gemm_rows(st, "wfcT", c.da, EPI_BF16, c.dh[:Mr], n_seq, Lx, scratch=c.dh)
+            else:
+                self._gemm(st, "wfcT", c.da[:Mr], EPI_BF16, c.dh[:Mr])
+        ops.layernorm_bwd(c.dh[:Mr], s.x_mid, s.mean2, s.rstd2, blk.ln_2.weight,
+                          c.dx_mid[:Mr], _rows(c.dx_midb, Mr), dres=gx)
 
-    def sync_grads(self):
-        """Make the current stream wait for the PEFT-gradient work on the side stream."""
-        if self._gs is not None:
-            torch.cuda.current_stream(self._gs.device).wait_stream(self._gs)
+    def _bwd_attn(self, c, li, s, ox, oxb, bufs, first):
+        """Backward of x_mid = x_in + [A](out_proj(attn(ln_1(x_in)))) from c.dx_mid / c.dx_midb
+        into (ox, oxb), the output pair of bufs. first (layer 0 of a tower whose input is
+        frozen): stops after the last PEFT gradient and returns False."""
+        blk, st, attn = self.blocks[li], self.staged[li], self.blocks[li].attn
+        n_seq, H, Lx = c.n_seq, self.n_head, c.L + s.P
+        Mx = n_seq * Lx
+        Mr = n_seq if s.rows else Mx
+        dh, dO, dqkv, dx_mid = c.dh, c.dO, c.dqkv, c.dx_mid
+        if self.variant == "adapter":
+            dY = self._adapter_bwd(c, blk, st, dx_mid[:Mr] if c.nocopy else c.dx_midb[:Mr],
+                                   s.hd1, s.z1, s.keep, None if first else c.dz[:Mr],
+                                   pad=(n_seq, Lx) if s.rows else None)
+        else:
+            dY = c.dx_midb[:Mx]
+        if first and self.variant != "lora":
+            return False
+        ops.gemm_nt(dY, st.woT, EPI_BF16, dO[:Mr])
+        if self.variant == "lora":
+            self._lora_grad(c, dY, s.O, attn.out_proj.lora_A, attn.out_proj.lora_B,
+                            attn.scaling, st.lora_out)
+        if s.rows:  # (da and dh are free: the MLP chain is done, QKV dX rewrites dh below)
+            qd = self._attn_bwd_rows(s, dO[:Mr], dqkv[:Mx], n_seq, Lx, c.da, dh)
+        elif c.q_dqkv is not None and not first:
+            qd = ops.attn_bwd_fp8(s.qkv, s.O, dO[:Mx], s.lse, c.q_dqkv.narrow(Mx), n_seq,
+                                  Lx, H, self.causal)
+        else:
+            qd = None
+            ops.attn_bwd(s.qkv, s.O, dO[:Mx], s.lse, dqkv[:Mx], n_seq, Lx, H, self.causal)
+        if self.variant == "lora":
+            self._lora_grad(c, dqkv[:Mx], s.h1, attn.in_proj_weight_lora_A,
+                            attn.in_proj_weight_lora_B, attn.scaling, st.lora_in)
+        if first:
+            return False
+        if qd is not None:
+            ops.gemm_nt_fp8(qd, st.q["wqkvT"], EPI_BF16, dh[:Mx])
+        else:
+            self._gemm(st, "wqkvT", dqkv[:Mx], EPI_BF16, dh[:Mx])
+        dres1 = dx_mid[:Mx]
+        if s.rows:
+            # into the caller's zero buffer (never an output buffer: keep_input)
+            dres1 = self._spread(dx_mid[:Mr], n_seq, Lx, dst=bufs.incoming(Mx), fill=None)
+        if c.fuse_ln_q and s.R is None and not s.P:
+            bufs.set_q(ops.layernorm_bwd_fp8(dh[:Mx], s.x_in, s.mean1, s.rstd1, blk.ln_1.weight,
+                                             ox, oxb, bufs.q_mat(Mx), dres=dx_mid[:Mx]))
+        else:
+            bufs.set_q(None)
+            ops.layernorm_bwd(dh[:Mx], s.x_in, s.mean1, s.rstd1, blk.ln_1.weight, ox, oxb,
+                              dres=dres1)
+        return True
 
-    def _side(self):
-        """Context for launching gradient reductions: the side stream (after the work that
-        produced their inputs on the current stream) or the current stream."""
-        gs = self._gs
-        if gs is None:
-            return _Null()
-        gs.wait_stream(torch.cuda.current_stream(gs.device))
-        return torch.cuda.stream(gs)
-
-    @staticmethod
-    def _grad(grads, p):
-        g = grads.get(p)
-        if g is None:
-            raise KeyError("missing gradient buffer for a trainable parameter")
-        return g
-
-    def _adapter_bwd(self, blk, st, gout, h, z, keep, dz, grads, pad=None):
+    def _adapter_bwd(self, c, blk, st, gout, h, z, keep, dz, pad=None):
         """pad = (n_seq, L): gout, h and z hold row 0 of every sequence only (the compact last
         block: _wgrad_rows). The weight-gradient launch and its fills are on the side stream."""
         ad = blk.adaptmlp
         M = gout.shape[0]
         dpre = _empty((M, ad.down_size), self.dt, gout.device)
         ops.adapter_bwd(gout, h, st.wuT, st.wdT, ad.scale, keep, dpre, dz)  # dz None: dpre only
-        with self._side():
-            if self._gs is not None:
-                dpre.record_stream(self._gs)
+        with c.side():
+            if c.gs is not None:
+                dpre.record_stream(c.gs)
             if pad is not None:
                 gout, h, z, dpre = self._wgrad_rows(*pad, gout, h, z, dpre)
-            ops.adapter_wgrad(gout, h, z, dpre, ad.scale, *(self._grad(grads, p) for p in (
+            ops.adapter_wgrad(gout, h, z, dpre, ad.scale, *(c.grad(p) for p in (
                 ad.up_proj.weight, ad.up_proj.bias, ad.down_proj.weight, ad.down_proj.bias)),
-                gscale=self._gscale)
+                gscale=c.gscale)
         return dz
 
     # ------------------------------------------------------------------ the compact last block
@@ -799,18 +984,18 @@ class BlockStack:
         bf16). The blanked launch borrows da / dh for dO / O: zero off row 0 (those rows' Delta, dP
         and dS are exact zeros, as in the full path) and lse = 1e30 (P = 0, as for padded rows)."""
         H, Mx = self.n_head, n_seq * L
-        args = (s["qkv"], s["O"], dO, s["lse"], dqkv, n_seq, L, H, 0, self.causal)
+        args = (s.qkv, s.O, dO, s.lse, dqkv, n_seq, L, H, 0, self.causal)
         if self.ROW_BWD:
             ops.attn_row_bwd(*args)
         elif not (self.ROWS_EXACT and ops.attn_bwd_live_row(*args)):
-            Of = self._spread(s["O"], n_seq, L, dst=dh[:Mx])
+            Of = self._spread(s.O, n_seq, L, dst=dh[:Mx])
             dOf = self._spread(dO, n_seq, L, dst=da.view(-1)[:Mx * dO.shape[1]].view(Mx, -1))
-            lsef = self._spread(s["lse"].view(-1, 1), n_seq * H, L, fill=1e30).view(-1, L)
-            ops.attn_bwd(s["qkv"], Of, dOf, lsef, dqkv, n_seq, L, H, self.causal)
+            lsef = self._spread(s.lse.view(-1, 1), n_seq * H, L, fill=1e30).view(-1, L)
+            ops.attn_bwd(s.qkv, Of, dOf, lsef, dqkv, n_seq, L, H, self.causal)
 
     def _wgrad_rows(self, n_seq, L, *operands):
         """The adapter weight-gradient operands ([n_seq, W] each) as the launch reads them:
-        blanked into fresh buffers (on the side stream under _side()), or under ROW_BWD as they
+        blanked into fresh buffers (on the side stream under _Backward.side()), or under ROW_BWD as they
         are. A live-rows weight-gradient walker goes here."""
         return operands if self.ROW_BWD else tuple(self._spread(t, n_seq, L) for t in operands)
 
@@ -846,7 +1031,7 @@ class BlockStack:
                     return False
         return True
 
-    def _lora_grad(self, dY, X, A, B, scaling, grads, padded):
+    def _lora_grad(self, c, dY, X, A, B, scaling, padded):
         """Rank-r LoRA gradients (lora.py:838-839, 1073-1074 autograd): one pass over X and dY
         (ops.lora_grad_1p: XA = X A^T and dYB = dY B per 32-row block, dB += s dY^T XA and
         dA += s dYB^T X from the same staged rows), or for shapes it does not cover four
@@ -856,25 +1041,24 @@ class BlockStack:
         M = dY.shape[0]
         r, K = A.shape
         N = B.shape[0]
-        gsc = self._gscale  # dY carries the half residual gradient's scale
+        gsc = c.gscale  # dY carries the half residual gradient's scale
         if self._lora_1p(r, K, N):
-            with self._side():
-                ops.lora_grad_1p(dY, X, a_pad, bt_pad, r, scaling, self._grad(grads, A),
-                                 self._grad(grads, B), gscale=gsc)
+            with c.side():
+                ops.lora_grad_1p(dY, X, a_pad, bt_pad, r, scaling, c.grad(A), c.grad(B),
+                                 gscale=gsc)
             return
         if gsc is not None:
             raise ValueError("a scaled LoRA gradient runs the one-pass kernel only")
-        with self._side():
+        with c.side():
             xa = _empty((M, 64), self.dt, dY.device)
             dyb = _empty((M, 64), self.dt, dY.device)
-            gs = self._gs
-            if gs is not None:
-                xa.record_stream(gs)
-                dyb.record_stream(gs)
+            if c.gs is not None:
+                xa.record_stream(c.gs)
+                dyb.record_stream(c.gs)
             ops.gemm_nt(X, a_pad, EPI_BF16, xa)
             ops.gemm_nt(dY, bt_pad, EPI_BF16, dyb)
-            ops.gemm_tn(dY, xa, self._grad(grads, B), alpha=scaling)
-            ops.gemm_tn(dyb, X, self._grad(grads, A), alpha=scaling)
+            ops.gemm_tn(dY, xa, c.grad(B), alpha=scaling)
+            ops.gemm_tn(dyb, X, c.grad(A), alpha=scaling)
 
 
 class ScaledGrads:
@@ -1161,16 +1345,16 @@ class ImageTower:
                         mean=_empty((M,), F32, x0.device), rstd=_empty((M,), F32, x0.device))
         x, saved = self.stack.forward(x0, n, L, save, training, prompts=prompts, replace=replace,
                                       first_ln1=first_ln1, last_ln=last, last_rows=rows)
-        if rows:  # x [n, D]: the CLS rows
+        # rows: x [n, D] holds the CLS rows only, and so do the fused ln_post's outputs
+        if last is not None and self.stack.last_ln_fused(x0.shape[1], prompts):
+            lnp, mean, rstd = last["y"], last["mean"], last["rstd"]
             cls_idx = torch.arange(n, device=x.device, dtype=torch.int32) * L
-            if last is not None and last.get("done"):
-                lnp, mean, rstd = last["y"], last["mean"], last["rstd"]
-            else:
-                lnp, _, mean, rstd = self._ln_post(x, n, 1, self.stack.dt)
-        elif last is not None and last.get("done"):
+            if not rows:
+                ci = cls_idx.long()
+                lnp, mean, rstd = lnp[ci], mean[ci], rstd[ci]
+        elif rows:
             cls_idx = torch.arange(n, device=x.device, dtype=torch.int32) * L
-            ci = cls_idx.long()
-            lnp, mean, rstd = last["y"][ci], last["mean"][ci], last["rstd"][ci]
+            lnp, _, mean, rstd = self._ln_post(x, n, 1, self.stack.dt)
         else:
             lnp, cls_idx, mean, rstd = self._ln_post(x, n, L, self.stack.dt)
         f = _empty((n, self.projT.shape[0]), F32, x.device)

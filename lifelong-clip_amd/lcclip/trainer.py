@@ -13,6 +13,7 @@ is a single all-reduce (1.47 MB LoRA / 7.93 MB adapter for ViT-B/16 both towers)
 from __future__ import annotations
 
 import os
+from contextlib import nullcontext
 
 import torch
 
@@ -21,14 +22,6 @@ from .dp import DataParallel, layer_ranges
 from .adapter_clip import freeze_backbone
 from .ops import F32
 from .textcache import TokenFeatureCache
-
-
-class _nullctx:
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        return False
 
 
 def remap_labels(labels, class_list=None):
@@ -144,7 +137,7 @@ class OnlineTrainer:
         cached = self._cached_text(tokens)
         if cached is None:
             train_t = bool(self.txt.stack.trainable_params())
-            with torch.cuda.stream(side) if side is not None else _nullctx():
+            with torch.cuda.stream(side) if side is not None else nullcontext():
                 f_t, ct = self.txt.forward(tok_in, save=train_t, training=True)
         f_i, ci = self.img.forward(images, save=True, training=True)
         if side is not None:
@@ -178,15 +171,16 @@ class OnlineTrainer:
         if train_txt:
             if side is not None:
                 side.wait_stream(main)
-            with torch.cuda.stream(side) if side is not None else _nullctx():
+            with torch.cuda.stream(side) if side is not None else nullcontext():
                 ops.head_feat_grad(dlog, 1, C, img_n, txt_n, nt, self.logit_scale, d_tp[:C])
                 w_dt = dp.sum_async(d_tp) if self.shard_text else None
                 if w_dt is not None:
                     w_dt.wait()  # the current (text) stream waits for the dL/dT all-reduce
                 self.txt.backward(ct, d_tp[lo:hi].contiguous(), self.grads)
         if self.img.stack.trainable_params():
-            self.img.backward(ci, d_i, self.grads, on_layer=self._img_bucket_hook(),
-                              grad_stream=self._grad_stream(dev))
+            gs = self._grad_stream(dev)
+            self.img.backward(ci, d_i, self.grads, on_layer=self._img_bucket_hook(gs),
+                              grad_stream=gs)
         if side is not None:
             main.wait_stream(side)
         dp.launch_bucket(self.flat_g, *self.txt_range)
@@ -258,8 +252,9 @@ class OnlineTrainer:
             self._side = self._new_stream(dev)
         return self._side
 
-    def _img_bucket_hook(self):
-        """Launch the all-reduce of image layers [li, prev) every bucket_layers layers."""
+    def _img_bucket_hook(self, gs):
+        """Launch the all-reduce of image layers [li, prev) every bucket_layers layers. gs: the
+        grad_stream of the backward that calls the hook (None: none)."""
         if not self.distributed:
             return None
         state = {"hi": len(self.img_ranges)}
@@ -268,7 +263,6 @@ class OnlineTrainer:
             if li % self.bucket_layers == 0:
                 lo_r = self.img_ranges[li][0]
                 hi_r = self.img_ranges[state["hi"] - 1][1]
-                gs = getattr(self.img.stack, "_gs", None)
                 if gs is None:
                     self.dp.launch_bucket(self.flat_g, lo_r, hi_r)
                 else:

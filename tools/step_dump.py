@@ -1,15 +1,21 @@
-"""One OnlineTrainer.forward_backward with every lcclip.ops call recorded (dev tool): for
-comparing two checkouts that must issue the same launches and compute the same bits.
+"""One training step with every lcclip.ops call recorded (dev tool): for comparing two checkouts
+that must issue the same launches and compute the same bits.
 
-  python tools/step_dump.py OUT [--model tiny|w768] [--method adapter|lora]
-                                [--image-precision bf16|fp16]
+  python tools/step_dump.py OUT [--model tiny|w768] [--method adapter|lora|mvp|maple]
+                                [--image-precision bf16|fp16] [--use-last-layer 0|1]
+                                [--text-precision fp16|bf16] [--precision bf16|fp8]
 
-The models of tests/test_last_rows_exact_gpu.py (the tiny golden model, or 2 layers at width 768;
-4 images, dropout 0.1, the dropout seed counter at its start); the LCCLIP_* knobs come from the
-environment. Writes OUT.trace.txt, one line per call through a public function of lcclip.ops —
-name, tensor arguments as dtype[shape], scalar arguments, and the stream it was issued on (main:
-the one current at the start; side1, side2, ...: the others in order of appearance) — and
-OUT.npz: loss, probs and every trainable parameter's gradient."""
+adapter / lora: one OnlineTrainer.forward_backward on the models of
+tests/test_last_rows_exact_gpu.py (the tiny golden model, or 2 layers at width 768; 4 images,
+dropout 0.1, the dropout seed counter at its start). mvp: the tiny MVP model of
+tests/test_mvp_gpu.py (--use-last-layer), one forward, loss_fn and .backward(). maple: the tiny
+MaPLe model of tests/test_maple_gpu.py (--text-precision), or with --precision fp8 the tiny fp8
+model of test_maple_fp8_tiny; one forward, cross-entropy and .backward(). The LCCLIP_* knobs come
+from the environment. Writes OUT.trace.txt, one line per call through a public function of
+lcclip.ops — name, tensor arguments as dtype[shape], scalar arguments, and the stream it was
+issued on (main: the one current at the start; side1, side2, ...: the others in order of
+appearance) — and OUT.npz: loss, probs / logits, every trainable parameter's gradient and
+max_mem, torch.cuda.max_memory_allocated() of the step."""
 import argparse
 import inspect
 import itertools
@@ -28,24 +34,91 @@ from oracle import clip_oracle as o  # noqa: E402
 ap = argparse.ArgumentParser()
 ap.add_argument("out")
 ap.add_argument("--model", default="tiny", choices=["tiny", "w768"])
-ap.add_argument("--method", default="adapter", choices=["adapter", "lora"])
+ap.add_argument("--method", default="adapter", choices=["adapter", "lora", "mvp", "maple"])
 ap.add_argument("--image-precision", default="bf16", choices=["bf16", "fp16"])
+ap.add_argument("--use-last-layer", type=int, default=1, choices=[0, 1])
+ap.add_argument("--text-precision", default="fp16", choices=["fp16", "bf16"])
+ap.add_argument("--precision", default="bf16", choices=["bf16", "fp8"])
 a = ap.parse_args()
 
 dev = torch.device("cuda:0")
-if a.model == "tiny":
-    d = np.load(os.path.join(ROOT, "tests", "golden", "tiny_clip.npz"))
-    sd = {k[3:]: torch.from_numpy(d[k]) for k in d.files if k.startswith("sd/")}
-    sd = {k: sd[k] for k in o.param_shapes(o.TINY, "adapter", "both")}
-    if a.method == "lora":
-        sd = o.synthetic_state_dict(o.TINY, "lora", "both", seed=3)
-    img = o.synthetic_images(4, o.TINY.image_resolution, seed=28)
-    tok = torch.from_numpy(d["tokens"])
-else:
-    cfg = o.ClipConfig(vision_layers=2, transformer_layers=2)
-    sd = o.synthetic_state_dict(cfg, a.method, "both", seed=17)
-    img, tok = o.synthetic_images(4, 224, seed=18), o.synthetic_tokens(4, 77, seed=19)
-y = torch.arange(4) % tok.shape[0]
+
+
+def adapter_step():
+    if a.model == "tiny":
+        d = np.load(os.path.join(ROOT, "tests", "golden", "tiny_clip.npz"))
+        sd = {k[3:]: torch.from_numpy(d[k]) for k in d.files if k.startswith("sd/")}
+        sd = {k: sd[k] for k in o.param_shapes(o.TINY, "adapter", "both")}
+        if a.method == "lora":
+            sd = o.synthetic_state_dict(o.TINY, "lora", "both", seed=3)
+        img = o.synthetic_images(4, o.TINY.image_resolution, seed=28)
+        tok = torch.from_numpy(d["tokens"])
+    else:
+        cfg = o.ClipConfig(vision_layers=2, transformer_layers=2)
+        sd = o.synthetic_state_dict(cfg, a.method, "both", seed=17)
+        img, tok = o.synthetic_images(4, 224, seed=18), o.synthetic_tokens(4, 77, seed=19)
+    y = torch.arange(4) % tok.shape[0]
+    w = AdapterCLIP.from_state_dict(sd, a.method, "both", device=dev,
+                                    image_precision=a.image_precision)
+    tr = OnlineTrainer(set_adapter_dropout(w, 0.1))
+    named = [(n, p) for n, p in w.model.named_parameters() if p.requires_grad]
+
+    def step():
+        loss, probs = tr.forward_backward(img.to(dev), y.to(dev), tok.to(dev))
+        return {"loss": loss, "probs": probs}, {n: tr.grads[p] for n, p in named}
+    return step
+
+
+def mvp_step():
+    from lcclip.mvp_clip import CLIP_MVP
+    cfg = o.TINY_MVP
+    sd, mv = o.synthetic_state_dict(cfg, seed=21), o.mvp_params(cfg, seed=3)
+    img = o.synthetic_images(3, cfg.image_resolution, seed=5).to(dev)
+    tok = o.synthetic_tokens(4, cfg.context_length, seed=5, vocab=cfg.vocab_size).to(dev)
+    y = torch.tensor([0, 3, 1], device=dev)
+    m = CLIP_MVP.from_state_dict(sd, device=dev, num_classes=mv["mask"].shape[1],
+                                 task_num=mv["key"].shape[0],
+                                 use_last_layer=bool(a.use_last_layer))
+    with torch.no_grad():
+        for k in ("key", "mask", "g_prompts", "e_prompts"):
+            getattr(m, k).copy_(mv[k])
+    m.train()
+    m.text_tokens = tok
+
+    def step():
+        logits = m(img, tok)
+        loss = m.loss_fn(logits, y)
+        loss.backward()
+        return ({"loss": loss, "logits": logits},
+                {n: p.grad for n, p in m.named_parameters() if p.requires_grad})
+    return step
+
+
+def maple_step():
+    import torch.nn.functional as F
+    from lcclip.maple import MaPLe
+    fp8 = a.precision == "fp8"
+    cfg, s_sd, s_mp, s_in = (o.TINY_MAPLE8, 51, 4, 8) if fp8 else (o.TINY_MAPLE, 41, 2, 6)
+    sd, mp = o.synthetic_state_dict(cfg, seed=s_sd), o.maple_params(cfg, seed=s_mp)
+    img = o.synthetic_images(3, cfg.image_resolution, seed=s_in).to(dev)
+    tok = o.synthetic_tokens(4, 77, seed=s_in, vocab=cfg.vocab_size).to(dev)
+    y = torch.tensor([0, 2, 3], device=dev)
+    kw = {"precision": "fp8"} if fp8 else {"text_precision": a.text_precision}
+    m = MaPLe.from_state_dict(sd, device=dev, **kw)
+    params = dict(m.named_parameters())
+    with torch.no_grad():
+        for k, name in o.MAPLE_TO_MODULE.items():
+            params[name].copy_(mp[k])
+    m.set_tokenized_prompts(tok)
+
+    def step():
+        logits = m(img)
+        loss = F.cross_entropy(logits, y)
+        loss.backward()
+        return ({"loss": loss, "logits": logits},
+                {n: p.grad for n, p in m.named_parameters() if p.requires_grad})
+    return step
+
 
 trace, streams = [], {torch.cuda.current_stream(dev).cuda_stream: "main"}
 
@@ -75,15 +148,18 @@ for name, fn in inspect.getmembers(ops, inspect.isfunction):
         setattr(ops, name, recorded(name, fn))
 
 engine._seed_counter = itertools.count(1)
-w = AdapterCLIP.from_state_dict(sd, a.method, "both", device=dev,
-                                image_precision=a.image_precision)
-tr = OnlineTrainer(set_adapter_dropout(w, 0.1))
-loss, probs = tr.forward_backward(img.to(dev), y.to(dev), tok.to(dev))
+step = {"mvp": mvp_step, "maple": maple_step}.get(a.method, adapter_step)()
 torch.cuda.synchronize()
-out = {"loss": loss, "probs": probs}
-out.update({"grad/" + n: tr.grads[p] for n, p in w.model.named_parameters() if p.requires_grad})
+torch.cuda.reset_peak_memory_stats(dev)
+out, grads = step()
+torch.cuda.synchronize()
+max_mem = torch.cuda.max_memory_allocated(dev)
+loss = out["loss"]
+out.update({"grad/" + n: g for n, g in grads.items()})
 os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-np.savez(a.out + ".npz", **{k: v.detach().float().cpu().numpy() for k, v in out.items()})
+np.savez(a.out + ".npz", max_mem=np.int64(max_mem),
+         **{k: v.detach().float().cpu().numpy() for k, v in out.items()})
 with open(a.out + ".trace.txt", "w") as f:
     f.write("\n".join(trace) + "\n")
-print(f"{a.out}: {len(trace)} calls, loss {loss.item():.9g}, streams {sorted(streams.values())}")
+print(f"{a.out}: {len(trace)} calls, loss {loss.item():.9g}, max_memory_allocated {max_mem}, "
+      f"streams {sorted(streams.values())}")
