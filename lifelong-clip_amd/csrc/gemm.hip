@@ -22,33 +22,23 @@
 #include <stdlib.h>
 #include <type_traits>
 
-enum {
-  EPI_BF16 = 0,        // out0 bf16 = acc*alpha + bias
-  EPI_F32 = 1,         // out0 f32  = acc*alpha + bias
-  EPI_RESID = 2,       // out0 f32  = aux_f32 + acc*alpha + bias          (residual add)
-  EPI_GELU = 3,        // out0 bf16 = pre = acc+bias ; out1 bf16 = quick_gelu(pre)
-  EPI_GELU_BWD = 4,    // out0 bf16 = (acc*alpha) * quick_gelu'(aux_bf16)
-  EPI_BF16_F32 = 5,    // out0 bf16 and out1 f32 of acc*alpha + bias
-  EPI_GELU_D = 6,      // out0 bf16 = quick_gelu'(pre) ; out1 bf16 = quick_gelu(pre), pre = acc+bias
-  EPI_MUL = 7,         // out0 bf16 = (acc*alpha) * aux_bf16
-  // fused adapter epilogues (internal; adapter.py:59-72 as two skinny GEMMs)
-  EPI_AD_DOWN = 8,     // out0 bf16 = relu(acc + bias) * dropmask(seed, m, n) / keep
-  EPI_AD_UP = 9,       // out0 f32 = aux_f32 + aux2_bf16 + scale * (acc + bias)
-  EPI_AD_MASK = 10,    // out0 bf16 = aux_bf16 > 0 ? alpha * acc / keep : 0
-  EPI_AD_ADD = 11,     // out0 bf16 = aux_bf16 + acc
-  // fp8-output epilogues of the fp8 GEMM (MaPLe's fp8 mode): out1 = e4m3 codes (ldo1 in bytes)
-  // + E8M0 scales (ep.q_scale, ep.q_rows) of the bf16-rounded value, bit-identical to the bf16
-  // epilogue followed by quant_fp8 (quant.hip) — the next fp8 GEMM's A operand straight from here
-  EPI_GELU_D_Q8 = 12,  // out0 bf16 = quick_gelu'(pre) ; out1 fp8 = quick_gelu(pre), pre = acc+bias
-  EPI_MUL_Q8 = 13,     // out1 fp8 = (acc*alpha) * aux_bf16 (out0 unused)
-  // the half residual stream (lc_common.h xres): out0 half = aux_half + acc*alpha + bias
-  EPI_RESID16 = 14,
-};
-
 namespace {
 
 constexpr int BK = 64;
 
+// The epilogues a kernel family is instantiated for, stated once next to its kernel.
+// dispatch_epi calls f(std::integral_constant<int, E>) for the E of the list that equals the
+// run-time epi; an epi outside the list is LC_EINVAL (nothing launched).
+template <int... Es>
+struct EpiList {};
+template <int... Es>
+constexpr bool epi_in(EpiList<Es...>, int epi) { return ((epi == Es) || ...); }
+template <class F, int... Es>
+int dispatch_epi(EpiList<Es...>, int epi, F&& f) {
+  int rc = LC_EINVAL;
+  (void)((epi == Es && (rc = f(std::integral_constant<int, Es>{}), true)) || ...);
+  return rc;
+}
 
 LC_DEV int swz(int row, int chunk) { return chunk ^ ((row >> 1) & 7); }
 
@@ -481,6 +471,9 @@ gemm_nt_kernel(int M, int N, int K, const bf16_t* __restrict__ A, long lda,
   store_tile<BM, BN, WM, WN, EPI, PASS_MAX>(acc, smem, SMEM, m0, n0, M, bias, alpha, out0, ldo0,
                                             out1, ldo1, aux, ldaux, ep);
 }
+using NtEpis = EpiList<EPI_BF16, EPI_F32, EPI_RESID, EPI_RESID16, EPI_GELU, EPI_GELU_BWD,
+                        EPI_BF16_F32, EPI_GELU_D, EPI_MUL, EPI_AD_DOWN, EPI_AD_UP, EPI_AD_MASK,
+                        EPI_AD_ADD>;
 
 // ---------------------------------------------------------------------------------------------
 // Ping-pong GEMM (BM x BN = 256 x 256 or 128 x 256..., 8 waves as 2 x 4).
@@ -754,6 +747,8 @@ gemm_pp_kernel(int M, int N, int K, const bf16_t* __restrict__ A, long lda,
   store_tile<BM, BN, WM, WN, EPI>(acc, smem, NSLOT * SLOT, m0, n0, M, bias, alpha, out0, ldo0,
                                   out1, ldo1, aux, ldaux, ep);
 }
+using PpEpis = EpiList<EPI_BF16, EPI_F32, EPI_RESID, EPI_GELU, EPI_GELU_BWD, EPI_BF16_F32,
+                        EPI_GELU_D, EPI_MUL, EPI_AD_DOWN, EPI_AD_UP, EPI_AD_MASK, EPI_AD_ADD>;
 
 // ---------------------------------------------------------------------------------------------
 // Phase-interleaved GEMM, bf16 or block-scaled fp8 (256 x 256 tile, 512 threads).
@@ -1230,6 +1225,10 @@ gemm8_kernel(int M, int N, int K, const void* __restrict__ Av, long lda,
     }
   }
 }
+// (the bf16 route takes all but the two fp8-output ones, g8_epilogue; stream-K: the plain three)
+using G8Epis = EpiList<EPI_BF16, EPI_F32, EPI_RESID, EPI_RESID16, EPI_GELU, EPI_GELU_D, EPI_MUL,
+                        EPI_GELU_D_Q8, EPI_MUL_Q8>;
+using G8SkEpis = EpiList<EPI_BF16, EPI_F32, EPI_RESID>;
 
 // ---------------------------------------------------------------------------------------------
 // 4-wave 256x256 GEMM (one wave per SIMD, each wave a 128x128 sub-tile: 64 accumulator tiles in
@@ -1416,6 +1415,7 @@ gemm_w4_kernel(int M, int N, int K, const bf16_t* __restrict__ A, long lda,
   store_tile<BM, BN, WM, WN, EPI>(acc, smem, NSLOT * SLOT, m0, n0, M, bias, alpha, out0, ldo0,
                                   out1, ldo1, aux, ldaux, ep);
 }
+using W4Epis = EpiList<EPI_BF16, EPI_F32, EPI_RESID, EPI_GELU_D, EPI_MUL>;
 
 // ---------------------------------------------------------------------------------------------
 // TN split-K GEMM: C[N1,N2] += alpha * sum_m A[m][n1] * B[m][n2].
@@ -1836,38 +1836,40 @@ void plan_tn(TnProb& p, int total_panels) {
   p.wgs = p.n_tiles * chunks;
 }
 
-template <int BM, int BN, int WM, int WN, int STAGES>
-int launch_nt(hipStream_t st, int epi, int M, int N, int K, const bf16_t* A, long lda,
-              const bf16_t* B, long ldb, const float* bias, float alpha, void* o0, long l0,
-              void* o1, long l1, const void* aux, long la, const EpiParams& ep) {
-  // the main-loop DMA descriptors span one tile of A / B rows with 32-bit byte offsets
-  LC_CHECK_ARG(lda < (1L << 22) && ldb < (1L << 22));
-  const int tiles = ((M + BM - 1) / BM) * (N / BN);
-  dim3 grid(tiles), block(64 * WM * WN);
-#define LC_NT_CASE(E)                                                                       \
-  case E:                                                                                     \
-    hipLaunchKernelGGL((gemm_nt_kernel<BM, BN, WM, WN, STAGES, E>), grid, block, 0, st, M, N, \
-                       K, A, lda, B, ldb, bias, alpha, o0, l0, o1, l1, aux, la, ep);          \
-    break;
-  switch (epi) {
-    LC_NT_CASE(EPI_BF16)
-    LC_NT_CASE(EPI_F32)
-    LC_NT_CASE(EPI_RESID)
-    LC_NT_CASE(EPI_RESID16)
-    LC_NT_CASE(EPI_GELU)
-    LC_NT_CASE(EPI_GELU_BWD)
-    LC_NT_CASE(EPI_BF16_F32)
-    LC_NT_CASE(EPI_GELU_D)
-    LC_NT_CASE(EPI_MUL)
-    LC_NT_CASE(EPI_AD_DOWN)
-    LC_NT_CASE(EPI_AD_UP)
-    LC_NT_CASE(EPI_AD_MASK)
-    LC_NT_CASE(EPI_AD_ADD)
-    default:
-      return LC_EINVAL;
+// gemm_tn_wide_kernel on one problem (b empty) or two of the same panel width, then the second
+// stage when the problems keep their partials in slots (b's are set whenever a's are).
+int launch_tn_wide(hipStream_t stream, const TnProb& a, const TnProb& b) {
+  const dim3 grid(a.wgs + b.wgs), block(512);
+  if (a.pw == 256) hipLaunchKernelGGL(gemm_tn_wide_kernel<256>, grid, block, 0, stream, a, b);
+  else hipLaunchKernelGGL(gemm_tn_wide_kernel<128>, grid, block, 0, stream, a, b);
+  if (a.part) {
+    const int outs = a.Nw * 64 + a.Nw + 64 + (b.part ? b.Nw * 64 + b.Nw + 64 : 0);
+    hipLaunchKernelGGL(tn_reduce_kernel, dim3((outs + 255) / 256), dim3(256), 0, stream, a, b);
   }
-#undef LC_NT_CASE
   LC_LAUNCH_RET();
+}
+
+// One GEMM kernel launch: the record expanded into the kernels' shared argument prefix
+// (M ... ldaux, ep), then the family's own tail (SplitK, Fp8Scales). AT: the kernel's operand
+// pointer type; es: bytes per operand element where the kernel takes byte strides (gemm8_kernel),
+// else 1. ep: the record's, or the launcher's copy with the route's group_m.
+template <class AT, class Kern, class... Tail>
+int launch(Kern kern, int grid, int block, const GemmArgs& g, long es, const EpiParams& ep,
+           const Tail&... tail) {
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(block), 0, g.stream, g.M, g.N, g.K,
+                     static_cast<const AT*>(g.A), g.lda * es, static_cast<const AT*>(g.B),
+                     g.ldb * es, g.bias, g.alpha, g.out0, g.ldo0, g.out1, g.ldo1, g.aux, g.ldaux,
+                     ep, tail...);
+  LC_LAUNCH_RET();
+}
+
+template <int BM, int BN, int WM, int WN, int STAGES>
+int launch_nt(const GemmArgs& g) {
+  const int tiles = ((g.M + BM - 1) / BM) * (g.N / BN);
+  return dispatch_epi(NtEpis{}, g.epi, [&](auto E) {
+    return launch<bf16_t>(gemm_nt_kernel<BM, BN, WM, WN, STAGES, E()>, tiles, 64 * WM * WN, g, 1,
+                          g.ep);
+  });
 }
 
 int g_split_mode = -1;  // LC_GEMM_SPLITK=0 disables the split-K tail (A/B experiments)
@@ -1939,7 +1941,7 @@ bool plan_sk(int tiles, int units, void* ws, long ws_bytes, SplitK& sk, int& G, 
   return true;
 }
 bool sk_wanted(int epi, int N, int K) {
-  if (epi != EPI_BF16 && epi != EPI_F32 && epi != EPI_RESID) return false;
+  if (!epi_in(G8SkEpis{}, epi)) return false;
   switch (g_sk_mode) {
     case 1: return N == 768 && K >= 2048;
     case 2: return N == 768;
@@ -1962,67 +1964,7 @@ int group_m(int N) {
   return N >= 2304 ? 8 : 1;
 }
 
-int launch_w4(hipStream_t st, int epi, int M, int N, int K, const bf16_t* A, long lda,
-              const bf16_t* B, long ldb, const float* bias, float alpha, void* o0, long l0,
-              void* o1, long l1, const void* aux, long la, const EpiParams& ep_in) {
-  EpiParams ep = ep_in;
-  ep.group_m = group_m(N);
-  const int tiles = ((M + 255) / 256) * (N / 256);
-  dim3 grid(tiles), block(256);
-#define LC_W4_CASE(E)                                                                          \
-  case E:                                                                                      \
-    hipLaunchKernelGGL((gemm_w4_kernel<E>), grid, block, 0, st, M, N, K, A, lda, B, ldb, bias, \
-                       alpha, o0, l0, o1, l1, aux, la, ep);                                    \
-    break;
-  switch (epi) {
-    LC_W4_CASE(EPI_BF16)
-    LC_W4_CASE(EPI_F32)
-    LC_W4_CASE(EPI_RESID)
-    LC_W4_CASE(EPI_GELU_D)
-    LC_W4_CASE(EPI_MUL)
-    default:
-      return LC_EINVAL;
-  }
-#undef LC_W4_CASE
-  LC_LAUNCH_RET();
-}
-
-int launch_pp(hipStream_t st, int epi, int M, int N, int K, const bf16_t* A, long lda,
-              const bf16_t* B, long ldb, const float* bias, float alpha, void* o0, long l0,
-              void* o1, long l1, const void* aux, long la, const EpiParams& ep, void* ws,
-              long ws_bytes) {
-  const int tiles = ((M + 255) / 256) * (N / 256);
-  const SplitK sk = plan_split(tiles, K / 32, 16, ws, ws_bytes);
-  dim3 grid(sk.dp_tiles + (tiles - sk.dp_tiles) * sk.splits), block(512);
-#define LC_PP_CASE(E)                                                                          \
-  case E:                                                                                      \
-    hipLaunchKernelGGL((gemm_pp_kernel<E>), grid, block, 0, st, M, N, K, A, lda, B, ldb, bias, \
-                       alpha, o0, l0, o1, l1, aux, la, ep, sk);                                \
-    break;
-  switch (epi) {
-    LC_PP_CASE(EPI_BF16)
-    LC_PP_CASE(EPI_F32)
-    LC_PP_CASE(EPI_RESID)
-    LC_PP_CASE(EPI_GELU)
-    LC_PP_CASE(EPI_GELU_BWD)
-    LC_PP_CASE(EPI_BF16_F32)
-    LC_PP_CASE(EPI_GELU_D)
-    LC_PP_CASE(EPI_MUL)
-    LC_PP_CASE(EPI_AD_DOWN)
-    LC_PP_CASE(EPI_AD_UP)
-    LC_PP_CASE(EPI_AD_MASK)
-    LC_PP_CASE(EPI_AD_ADD)
-    default:
-      return LC_EINVAL;
-  }
-#undef LC_PP_CASE
-  LC_LAUNCH_RET();
-}
-
-// Phase-interleaved 256x256 GEMM (gemm8_kernel). bf16: A, B bf16 with lda/ldb in elements;
-// fp8: A, B e4m3 with lda/ldb in bytes and their E8M0 scales in sc.
-// The split-K plan of a gemm8_kernel launch (launch_g8, and lc_gemm_nt_rows for the launch it
-// stands in for).
+// The split-K plan of a gemm8_kernel launch.
 template <bool FP8>
 SplitK g8_plan(int M, int N, int K, void* ws, long ws_bytes) {
   const int tiles = ((M + 255) / 256) * (N / 256);
@@ -2033,65 +1975,6 @@ SplitK g8_plan(int M, int N, int K, void* ws, long ws_bytes) {
     return e && atoi(e) > 0 ? atoi(e) : 8;
   }();
   return plan_split(tiles, units, split_min, ws, ws_bytes);
-}
-
-template <bool FP8>
-int launch_g8(hipStream_t st, int epi, int M, int N, int K, const void* A, long lda,
-              const void* B, long ldb, const float* bias, float alpha, void* o0, long l0,
-              void* o1, long l1, const void* aux, long la, const EpiParams& ep_in, void* ws,
-              long ws_bytes, const Fp8Scales& sc) {
-  EpiParams ep = ep_in;
-  ep.group_m = group_m(N);
-  const int tiles = ((M + 255) / 256) * (N / 256);
-  const int units = K / (FP8 ? 128 : 64);
-  const SplitK sk = g8_plan<FP8>(M, N, K, ws, ws_bytes);
-  const long ea = FP8 ? 1 : 2;  // bytes per element
-  // the main-loop DMA descriptors span one 256-row tile of A / B with 32-bit byte offsets
-  LC_CHECK_ARG(lda * ea < (1L << 23) && ldb * ea < (1L << 23));
-  if constexpr (!FP8) {
-    SplitK skm{};
-    int G = 0;
-    // mode 4: one workgroup per 256-row panel walking its N / 256 column tiles (hipBLASLt's
-    // N = 768 schedule: 197 workgroups at M = 50 432, no tile cut)
-    const int panels = g_sk_mode == 4 ? (M + 255) / 256 : 0;
-    if (sk_wanted(epi, N, K) && plan_sk(tiles, units, ws, ws_bytes, skm, G, panels)) {
-#define LC_G8SK_CASE(E)                                                                          \
-  case E:                                                                                        \
-    hipLaunchKernelGGL((gemm8_kernel<E, false, true>), dim3(G), dim3(512), 0, st, M, N, K, A,    \
-                       lda * ea, B, ldb * ea, bias, alpha, o0, l0, o1, l1, aux, la, ep, skm, sc); \
-    break;
-      switch (epi) {
-        LC_G8SK_CASE(EPI_BF16)
-        LC_G8SK_CASE(EPI_F32)
-        LC_G8SK_CASE(EPI_RESID)
-        default:
-          return LC_EINVAL;
-      }
-#undef LC_G8SK_CASE
-      LC_LAUNCH_RET();
-    }
-  }
-  dim3 grid(sk.dp_tiles + (tiles - sk.dp_tiles) * sk.splits), block(512);
-#define LC_G8_CASE(E)                                                                          \
-  case E:                                                                                      \
-    hipLaunchKernelGGL((gemm8_kernel<E, FP8>), grid, block, 0, st, M, N, K, A, lda * ea, B,    \
-                       ldb * ea, bias, alpha, o0, l0, o1, l1, aux, la, ep, sk, sc);            \
-    break;
-  switch (epi) {
-    LC_G8_CASE(EPI_BF16)
-    LC_G8_CASE(EPI_F32)
-    LC_G8_CASE(EPI_RESID)
-    LC_G8_CASE(EPI_RESID16)
-    LC_G8_CASE(EPI_GELU)
-    LC_G8_CASE(EPI_GELU_D)
-    LC_G8_CASE(EPI_MUL)
-    LC_G8_CASE(EPI_GELU_D_Q8)
-    LC_G8_CASE(EPI_MUL_Q8)
-    default:
-      return LC_EINVAL;
-  }
-#undef LC_G8_CASE
-  LC_LAUNCH_RET();
 }
 
 // tile-shape selector (env LC_GEMM_TILE forces one for experiments: 0 auto, 1 = 128x128x2,
@@ -2107,11 +1990,13 @@ int forced_tile() {
   return g_force_tile;
 }
 
-// the epilogues gemm8_kernel is instantiated for (the others of tile 8 run on the ping-pong kernel)
+// the epilogues the bf16 route runs on gemm8_kernel: its list less the fp8-output ones (the others
+// of tile 8 run on the ping-pong kernel)
 bool g8_epilogue(int epi) {
-  return epi == EPI_BF16 || epi == EPI_F32 || epi == EPI_RESID || epi == EPI_GELU ||
-         epi == EPI_GELU_D || epi == EPI_MUL || epi == EPI_RESID16;
+  return epi_in(G8Epis{}, epi) && epi != EPI_GELU_D_Q8 && epi != EPI_MUL_Q8;
 }
+
+EpiParams default_epi() { return EpiParams{nullptr, 0, 1.0f, 1.0f, 0, g_dbg}; }
 
 #ifndef LC_F16
 #ifndef LC_BLASLT_MIN_M  // (A/B builds override it)
@@ -2132,76 +2017,8 @@ bool blaslt_wanted(int tile, int epi, const float* bias, float alpha, int M, int
 }
 #endif
 
-int route_tile(int tile, int epi, int M, int N, int K);
-
-}  // namespace
-
-int lc_gemm_nt_ex(hipStream_t stream, int epi, int M, int N, int K, const void* A, long lda,
-                  const void* B, long ldb, const float* bias, float alpha, void* out0, long ldo0,
-                  void* out1, long ldo1, const void* aux, long ldaux, const EpiParams& ep,
-                  void* ws, long ws_bytes) {
-  LC_CHECK_ARG(M > 0 && N > 0 && K > 0 && K % 64 == 0 && N % 64 == 0);
-  LC_CHECK_ARG(lda % 8 == 0 && ldb % 8 == 0 && lda >= K && ldb >= K);
-  LC_CHECK_ARG(lda < (1L << 22) && ldb < (1L << 22));  // tile descriptors: 32-bit byte offsets
-  // epilogue rows are written / side inputs read 8 elements (16 B of bf16) per lane
-  LC_CHECK_ARG(ldo0 % 8 == 0 && ldo0 >= N);
-  // the epilogue's buffer descriptors span one 256-row tile with 32-bit byte offsets: 256 rows
-  // x ldo x 4 B (f32 outputs) must stay below 2^31 (num_records and the int offsets)
-  LC_CHECK_ARG(ldo0 < (1L << 21) && ldo1 < (1L << 21));
-  LC_CHECK_ARG((epi >= 0 && epi <= EPI_AD_ADD) || epi == EPI_RESID16);
-  if (epi == EPI_GELU || epi == EPI_BF16_F32 || epi == EPI_GELU_D)
-    LC_CHECK_ARG(out1 != nullptr && ldo1 >= N && ldo1 % 8 == 0);
-  if (epi == EPI_RESID || epi == EPI_GELU_BWD || epi == EPI_MUL || epi >= EPI_AD_UP)
-    LC_CHECK_ARG(aux != nullptr && ldaux >= N && ldaux % 8 == 0);
-  if (epi == EPI_AD_UP) LC_CHECK_ARG(ep.aux2 != nullptr && ep.ldaux2 >= N && ep.ldaux2 % 8 == 0);
-  auto a = static_cast<const bf16_t*>(A);
-  auto b = static_cast<const bf16_t*>(B);
-  int tile = forced_tile();
-#ifndef LC_F16
-  if (blaslt_wanted(tile, epi, bias, alpha, M, N, K, ws, ws_bytes) &&
-      lc_blaslt_nt_bf16(stream, M, N, K, a, lda, b, ldb, out0, ldo0,
-                        static_cast<char*>(ws) + LC_SPLITK_TICKET_BYTES,
-                        ws_bytes - LC_SPLITK_TICKET_BYTES))
-    return LC_OK;
-#endif
-  tile = route_tile(tile, epi, M, N, K);
-  switch (tile) {
-    case 1:
-      return launch_nt<128, 128, 2, 2, 2>(stream, epi, M, N, K, a, lda, b, ldb, bias, alpha, out0,
-                                          ldo0, out1, ldo1, aux, ldaux, ep);
-    case 2:
-      return launch_nt<256, 128, 4, 2, 3>(stream, epi, M, N, K, a, lda, b, ldb, bias, alpha, out0,
-                                          ldo0, out1, ldo1, aux, ldaux, ep);
-    case 3:
-      return launch_nt<256, 256, 2, 4, 2>(stream, epi, M, N, K, a, lda, b, ldb, bias, alpha, out0,
-                                          ldo0, out1, ldo1, aux, ldaux, ep);
-    case 7:
-      return launch_w4(stream, epi, M, N, K, a, lda, b, ldb, bias, alpha, out0, ldo0, out1, ldo1,
-                       aux, ldaux, ep);
-    case 5:
-    case 6:
-      return launch_pp(stream, epi, M, N, K, a, lda, b, ldb, bias, alpha, out0, ldo0, out1, ldo1,
-                       aux, ldaux, ep, ws, ws_bytes);
-    case 8:
-      if (!g8_epilogue(epi))
-        return launch_pp(stream, epi, M, N, K, a, lda, b, ldb, bias, alpha, out0, ldo0, out1, ldo1,
-                         aux, ldaux, ep, ws, ws_bytes);
-      return launch_g8<false>(stream, epi, M, N, K, a, lda, b, ldb, bias, alpha, out0, ldo0, out1,
-                              ldo1, aux, ldaux, ep, ws, ws_bytes, Fp8Scales{});
-    case 11:  // 128x64, one LDS stage
-      return launch_nt<128, 64, 4, 1, 1>(stream, epi, M, N, K, a, lda, b, ldb, bias, alpha, out0,
-                                         ldo0, out1, ldo1, aux, ldaux, ep);
-    default:
-      return launch_nt<128, 64, 4, 1, 2>(stream, epi, M, N, K, a, lda, b, ldb, bias, alpha, out0,
-                                         ldo0, out1, ldo1, aux, ldaux, ep);
-  }
-}
-
-namespace {
-
-// The kernel family lc_gemm_nt_ex runs a launch on (the lc_gemm_set_tile numbering): a forced
-// tile as it is, otherwise chosen from the shape. Shared with lc_gemm_nt_rows, which has to know
-// what a launch of M_full rows would have run on.
+// The tile a launch runs on (the lc_gemm_set_tile numbering): a forced tile as it is, otherwise
+// chosen from the shape.
 int route_tile(int tile, int epi, int M, int N, int K) {
   if (tile == 0) {
     // measured on the ViT-B/16 step shapes (tools/bench_gemm.py, M = 50 432): the 256x256
@@ -2254,31 +2071,117 @@ int route_tile(int tile, int epi, int M, int N, int K) {
   return tile;
 }
 
-// What a launch lc_gemm_nt_ex(epi, M, N, K, bias, alpha, ws) would run as, for lc_gemm_nt_rows
-// and lc_gemm_split_plan. ok: a schedule the row form can stand in for — gemm8_kernel's default
-// schedule with the returned plan, or a kernel family without any split (dp_tiles = every
-// 256x256 tile, S = 1: a launch at fewer rows sums each row in the same order). Not ok: a
-// forced tile, a stream-K mode, hipBLASLt, the ping-pong kernel (its own split rule).
-struct FullRoute {
-  bool ok;
-  SplitK sk;
-  int group_m;
+// Everything a launch needs beyond its arguments, decided once by route(): lc_gemm_nt_ex launches
+// what it says, lc_gemm_nt_rows and lc_gemm_split_plan read the same decision for the launch at
+// M_full rows they stand in for.
+enum Path {  // the lc_gemm_set_tile numbering where a tile names the kernel
+  PATH_NT_128x128 = 1,
+  PATH_NT_256x128 = 2,
+  PATH_NT_256x256 = 3,
+  PATH_NT_128x64 = 4,
+  PATH_PP = 5,  // ping-pong kernel
+  PATH_W4 = 7,  // 4-wave kernel
+  PATH_G8 = 8,  // gemm8_kernel, default schedule
+  PATH_NT_128x64_S1 = 11,  // 128x64, one LDS stage
+  PATH_G8_SK = 12,         // gemm8_kernel, stream-K
 };
-FullRoute full_route(int epi, const float* bias, float alpha, int M, int N, int K, void* ws,
-                     long ws_bytes) {
-  FullRoute r{false, SplitK{((M + 255) / 256) * ((N + 255) / 256), 1, nullptr, nullptr}, 1};
-  if (forced_tile() != 0 || g_sk_mode != 0) return r;
+struct Route {
+  int path;
+  bool blaslt;  // hipBLASLt is tried first; path runs when it declines
+  bool knob;    // a forced tile or a stream-K mode is set
+  SplitK sk;    // no split: dp_tiles = every 256x256 tile, S = 1
+  int group_m;  // ep.group_m of the 4-wave kernel and gemm8_kernel (the others keep the caller's)
+  int G;        // stream-K workgroups
+};
+
+Route route(const GemmArgs& g) {
+  const int M = g.M, N = g.N, K = g.K;
+  int tile = forced_tile();
+  Route r{PATH_NT_128x64, false, tile != 0 || g_sk_mode != 0,
+          SplitK{((M + 255) / 256) * ((N + 255) / 256), 1, nullptr, nullptr}, g.ep.group_m, 0};
 #ifndef LC_F16
-  if (blaslt_wanted(0, epi, bias, alpha, M, N, K, ws, ws_bytes)) return r;
+  r.blaslt = blaslt_wanted(tile, g.epi, g.bias, g.alpha, M, N, K, g.ws, g.ws_bytes);
 #endif
-  const int tile = route_tile(0, epi, M, N, K);
-  if (tile == 5 || tile == 6 || (tile == 8 && !g8_epilogue(epi))) return r;
-  r.ok = true;
-  if (tile == 8) {
-    r.sk = g8_plan<false>(M, N, K, ws, ws_bytes);
+  tile = route_tile(tile, g.epi, M, N, K);
+  const int tiles = ((M + 255) / 256) * (N / 256);
+  if (tile == 5 || tile == 6 || (tile == 8 && !g8_epilogue(g.epi))) {
+    r.path = PATH_PP;
+    r.sk = plan_split(tiles, K / 32, 16, g.ws, g.ws_bytes);
+  } else if (tile == 8) {
+    r.path = PATH_G8;
+    r.sk = g8_plan<false>(M, N, K, g.ws, g.ws_bytes);
     r.group_m = group_m(N);
+    // mode 4: one workgroup per 256-row panel walking its N / 256 column tiles (hipBLASLt's
+    // N = 768 schedule: 197 workgroups at M = 50 432, no tile cut)
+    const int panels = g_sk_mode == 4 ? (M + 255) / 256 : 0;
+    SplitK skm{};
+    if (sk_wanted(g.epi, N, K) && plan_sk(tiles, K / 64, g.ws, g.ws_bytes, skm, r.G, panels)) {
+      r.path = PATH_G8_SK;
+      r.sk = skm;
+    }
+  } else if (tile == 7) {
+    r.path = PATH_W4;
+    r.group_m = group_m(N);
+  } else if (tile == 1 || tile == 2 || tile == 3 || tile == 11) {
+    r.path = tile;
   }
   return r;
+}
+
+// A schedule the row form can stand in for: gemm8_kernel's default schedule with the route's
+// plan, or a kernel family without any split (a launch at fewer rows sums each row in the same
+// order). Not: a forced tile, a stream-K mode (wanted or not), hipBLASLt (taken or not), the
+// ping-pong kernel (its own split rule).
+bool rows_can_stand_in(const Route& r) { return !r.knob && !r.blaslt && r.path != PATH_PP; }
+
+int split_grid(const SplitK& sk, int tiles) {
+  return sk.dp_tiles + (tiles - sk.dp_tiles) * sk.splits;
+}
+
+int launch_w4(const GemmArgs& g, const Route& r) {
+  EpiParams ep = g.ep;
+  ep.group_m = r.group_m;
+  const int tiles = ((g.M + 255) / 256) * (g.N / 256);
+  return dispatch_epi(W4Epis{}, g.epi, [&](auto E) {
+    return launch<bf16_t>(gemm_w4_kernel<E()>, tiles, 256, g, 1, ep);
+  });
+}
+
+int launch_pp(const GemmArgs& g, const Route& r) {
+  const int tiles = ((g.M + 255) / 256) * (g.N / 256);
+  return dispatch_epi(PpEpis{}, g.epi, [&](auto E) {
+    return launch<bf16_t>(gemm_pp_kernel<E()>, split_grid(r.sk, tiles), 512, g, 1, g.ep, r.sk);
+  });
+}
+
+// Phase-interleaved 256x256 GEMM (gemm8_kernel). bf16: A, B bf16 with lda/ldb in elements;
+// fp8: A, B e4m3 with lda/ldb in bytes and their E8M0 scales in g.sc.
+template <bool FP8>
+int launch_g8(const GemmArgs& g, const Route& r) {
+  EpiParams ep = g.ep;
+  ep.group_m = r.group_m;
+  const long es = FP8 ? 1 : 2;  // bytes per element
+  if constexpr (!FP8) {
+    if (r.path == PATH_G8_SK)
+      return dispatch_epi(G8SkEpis{}, g.epi, [&](auto E) {
+        return launch<void>(gemm8_kernel<E(), false, true>, r.G, 512, g, es, ep, r.sk, g.sc);
+      });
+  }
+  const int tiles = ((g.M + 255) / 256) * (g.N / 256);
+  return dispatch_epi(G8Epis{}, g.epi, [&](auto E) {
+    return launch<void>(gemm8_kernel<E(), FP8>, split_grid(r.sk, tiles), 512, g, es, ep, r.sk,
+                        g.sc);
+  });
+}
+
+// Checks every launch passes, bf16 or fp8.
+int check_launch(const GemmArgs& g) {
+  LC_CHECK_ARG(g.ws == nullptr ||
+               (g.ws_bytes >= LC_SPLITK_TICKET_BYTES && ((uintptr_t)g.ws & 255) == 0));
+  // the epilogue's buffer descriptors span one 256-row tile with 32-bit byte offsets: 256 rows
+  // x ldo x 4 B (f32 outputs) must stay below 2^31 (num_records and the int offsets)
+  LC_CHECK_ARG(g.ldo0 < (1L << 21) && g.ldo1 < (1L << 21));
+  return LC_OK;
 }
 
 // Row fix-up of lc_gemm_nt_rows. Workgroup x takes the full launch's split-K tail tile
@@ -2326,15 +2229,53 @@ gemm_rows_fixup_kernel(int n, int N, int M_full, long mul, long add, int gm, int
 
 }  // namespace
 
+int lc_gemm_nt_ex(const GemmArgs& g) {
+  const int N = g.N, K = g.K, epi = g.epi;
+  LC_CHECK_ARG(g.M > 0 && N > 0 && K > 0 && K % 64 == 0 && N % 64 == 0);
+  LC_CHECK_ARG(g.lda % 8 == 0 && g.ldb % 8 == 0 && g.lda >= K && g.ldb >= K);
+  // the main-loop DMA descriptors span one tile of A / B rows with 32-bit byte offsets
+  LC_CHECK_ARG(g.lda < (1L << 22) && g.ldb < (1L << 22));
+  // epilogue rows are written / side inputs read 8 elements (16 B of bf16) per lane
+  LC_CHECK_ARG(g.ldo0 % 8 == 0 && g.ldo0 >= N);
+  if (int rc = check_launch(g)) return rc;
+  LC_CHECK_ARG((epi >= 0 && epi <= EPI_AD_ADD) || epi == EPI_RESID16);
+  if (epi == EPI_GELU || epi == EPI_BF16_F32 || epi == EPI_GELU_D)
+    LC_CHECK_ARG(g.out1 != nullptr && g.ldo1 >= N && g.ldo1 % 8 == 0);
+  if (epi == EPI_RESID || epi == EPI_GELU_BWD || epi == EPI_MUL || epi >= EPI_AD_UP)
+    LC_CHECK_ARG(g.aux != nullptr && g.ldaux >= N && g.ldaux % 8 == 0);
+  if (epi == EPI_AD_UP)
+    LC_CHECK_ARG(g.ep.aux2 != nullptr && g.ep.ldaux2 >= N && g.ep.ldaux2 % 8 == 0);
+  const Route r = route(g);
+#ifndef LC_F16
+  if (r.blaslt && lc_blaslt_nt_bf16(g.stream, g.M, N, K, g.A, g.lda, g.B, g.ldb, g.out0, g.ldo0,
+                                    static_cast<char*>(g.ws) + LC_SPLITK_TICKET_BYTES,
+                                    g.ws_bytes - LC_SPLITK_TICKET_BYTES))
+    return LC_OK;
+#endif
+  switch (r.path) {
+    case PATH_NT_128x128: return launch_nt<128, 128, 2, 2, 2>(g);
+    case PATH_NT_256x128: return launch_nt<256, 128, 4, 2, 3>(g);
+    case PATH_NT_256x256: return launch_nt<256, 256, 2, 4, 2>(g);
+    case PATH_W4: return launch_w4(g, r);
+    case PATH_PP: return launch_pp(g, r);
+    case PATH_G8:
+    case PATH_G8_SK: return launch_g8<false>(g, r);
+    case PATH_NT_128x64_S1: return launch_nt<128, 64, 4, 1, 1>(g);
+    default: return launch_nt<128, 64, 4, 1, 2>(g);
+  }
+}
+
 extern "C" {
 
 int lc_gemm_split_plan(int M, int N, int K, long ws_bytes, int* dp_tiles, int* splits) {
   LC_CHECK_ARG(M > 0 && N > 0 && K > 0 && K % 64 == 0 && N % 64 == 0 && dp_tiles && splits);
   // (the plan only does arithmetic on the workspace pointer: any non-null one serves)
   char dummy;
-  const FullRoute r = full_route(EPI_F32, nullptr, 1.0f, M, N, K,
-                                 ws_bytes > 0 ? &dummy : nullptr, ws_bytes);
-  if (!r.ok) return LC_EUNSUPPORTED;
+  GemmArgs g{};
+  g.epi = EPI_F32, g.M = M, g.N = N, g.K = K, g.alpha = 1.0f;
+  g.ws = ws_bytes > 0 ? &dummy : nullptr, g.ws_bytes = ws_bytes;
+  const Route r = route(g);
+  if (!rows_can_stand_in(r)) return LC_EUNSUPPORTED;
   *dp_tiles = r.sk.dp_tiles;
   *splits = r.sk.splits;
   return LC_OK;
@@ -2349,8 +2290,13 @@ int lc_gemm_nt_rows(hipStream_t stream, int epi, int n, int N, int K, const void
   LC_CHECK_ARG(out != nullptr && ((uintptr_t)out & 15) == 0 && ldo % 8 == 0 && ldo >= N);
   LC_CHECK_ARG(bias == nullptr || ((uintptr_t)bias & 15) == 0);
   if ((epi != EPI_BF16 && epi != EPI_F32) || alpha != 1.0f) return LC_EUNSUPPORTED;
-  const FullRoute r = full_route(epi, bias, alpha, M_full, N, K, ws, ws_bytes);
-  if (!r.ok) return LC_EUNSUPPORTED;
+  // every row as a launch without a split sums it; no workspace: this launch must not split
+  GemmArgs g{stream, epi, n, N, K, A, lda, B, ldb, bias, alpha, out, ldo, nullptr, 0, nullptr, 0,
+             default_epi()};
+  GemmArgs full = g;  // the launch the rows stand in for
+  full.M = M_full, full.ws = ws, full.ws_bytes = ws_bytes;
+  const Route r = route(full);
+  if (!rows_can_stand_in(r)) return LC_EUNSUPPORTED;
   const int S = r.sk.splits, nt = K / 64;
   const int tiles = ((M_full + 255) / 256) * (N / 256);
   float* part = nullptr;
@@ -2359,17 +2305,16 @@ int lc_gemm_nt_rows(hipStream_t stream, int epi, int n, int N, int K, const void
     if (LC_SPLITK_TICKET_BYTES + (long)S * n * N * 4 > ws_bytes) return LC_EUNSUPPORTED;
     part = reinterpret_cast<float*>(static_cast<char*>(ws) + LC_SPLITK_TICKET_BYTES);
   }
-  const EpiParams ep{nullptr, 0, 1.0f, 1.0f, 0, g_dbg};
-  // every row as a launch without a split sums it; no workspace: this launch must not split
-  int rc = lc_gemm_nt_ex(stream, epi, n, N, K, A, lda, B, ldb, bias, alpha, out, ldo, nullptr, 0,
-                         nullptr, 0, ep, nullptr, 0);
+  int rc = lc_gemm_nt_ex(g);
   if (rc != LC_OK || S == 1) return rc;
+  g.epi = EPI_F32, g.bias = nullptr, g.alpha = 1.0f, g.ldo0 = N;
   for (int s = 0; s < S; ++s) {  // k-tiles [tb, te) of slice s, as gemm8_kernel cuts them
     const int tb = s * nt / S, te = (s + 1) * nt / S;
-    rc = lc_gemm_nt_ex(stream, EPI_F32, n, N, (te - tb) * 64,
-                       static_cast<const bf16_t*>(A) + (long)tb * 64, lda,
-                       static_cast<const bf16_t*>(B) + (long)tb * 64, ldb, nullptr, 1.0f,
-                       part + (long)s * n * N, N, nullptr, 0, nullptr, 0, ep, nullptr, 0);
+    g.K = (te - tb) * 64;
+    g.A = static_cast<const bf16_t*>(A) + (long)tb * 64;
+    g.B = static_cast<const bf16_t*>(B) + (long)tb * 64;
+    g.out0 = part + (long)s * n * N;
+    rc = lc_gemm_nt_ex(g);
     if (rc != LC_OK) return rc;
   }
   dim3 grid(tiles - r.sk.dp_tiles), block(256);
@@ -2394,13 +2339,8 @@ int lc_gemm_nt_ws(hipStream_t stream, int epi, int M, int N, int K, const void* 
                   const void* B, long ldb, const float* bias, float alpha, void* out0, long ldo0,
                   void* out1, long ldo1, const void* aux, long ldaux, void* ws, long ws_bytes) {
   LC_CHECK_ARG((epi >= 0 && epi <= 7) || epi == EPI_RESID16);
-  LC_CHECK_ARG(ws == nullptr || (ws_bytes >= LC_SPLITK_TICKET_BYTES && ((uintptr_t)ws & 255) == 0));
-  // the epilogue's buffer descriptors span one 256-row tile with 32-bit byte offsets: 256 rows
-  // x ldo x 4 B (f32 outputs) must stay below 2^31 (num_records and the int offsets)
-  LC_CHECK_ARG(ldo0 < (1L << 21) && ldo1 < (1L << 21));
-  EpiParams ep{nullptr, 0, 1.0f, 1.0f, 0, g_dbg};
-  return lc_gemm_nt_ex(stream, epi, M, N, K, A, lda, B, ldb, bias, alpha, out0, ldo0, out1, ldo1,
-                       aux, ldaux, ep, ws, ws_bytes);
+  return lc_gemm_nt_ex({stream, epi, M, N, K, A, lda, B, ldb, bias, alpha, out0, ldo0, out1, ldo1,
+                        aux, ldaux, default_epi(), ws, ws_bytes});
 }
 
 int lc_gemm_set_debug(unsigned long long* p) {
@@ -2430,16 +2370,18 @@ int lc_gemm_nt_fp8(hipStream_t stream, int epi, int M, int N, int K, const void*
                  q_scale != nullptr && q_rows >= (M + 255) / 256 * 256 && q_rows % 256 == 0);
   if (epi == EPI_RESID || epi == EPI_MUL || epi == EPI_MUL_Q8 || epi == EPI_RESID16)
     LC_CHECK_ARG(aux != nullptr && ldaux >= N && ldaux % 8 == 0);
-  LC_CHECK_ARG(ws == nullptr || (ws_bytes >= LC_SPLITK_TICKET_BYTES && ((uintptr_t)ws & 255) == 0));
-  // the epilogue's buffer descriptors span one 256-row tile with 32-bit byte offsets: 256 rows
-  // x ldo x 4 B (f32 outputs) must stay below 2^31 (num_records and the int offsets)
-  LC_CHECK_ARG(ldo0 < (1L << 21) && ldo1 < (1L << 21));
-  EpiParams ep{nullptr, 0, 1.0f, 1.0f, 0, g_dbg};
-  ep.q_scale = q8 ? static_cast<uint8_t*>(q_scale) : nullptr;
-  ep.q_rows = q_rows;
-  Fp8Scales sc{static_cast<const uint8_t*>(sa), static_cast<const uint8_t*>(sb), sa_rows, sb_rows};
-  return launch_g8<true>(stream, epi, M, N, K, A, lda, B, ldb, bias, alpha, out0, ldo0, out1, ldo1,
-                         aux, ldaux, ep, ws, ws_bytes, sc);
+  // the main-loop DMA descriptors span one 256-row tile of A / B with 32-bit byte offsets
+  LC_CHECK_ARG(lda < (1L << 23) && ldb < (1L << 23));
+  GemmArgs g{stream, epi, M, N, K, A, lda, B, ldb, bias, alpha, out0, ldo0, out1, ldo1,
+             aux, ldaux, default_epi(), ws, ws_bytes,
+             Fp8Scales{static_cast<const uint8_t*>(sa), static_cast<const uint8_t*>(sb), sa_rows,
+                       sb_rows}};
+  if (int rc = check_launch(g)) return rc;
+  g.ep.q_scale = q8 ? static_cast<uint8_t*>(q_scale) : nullptr;
+  g.ep.q_rows = q_rows;
+  // always gemm8_kernel's default schedule: no shape router, never stream-K
+  return launch_g8<true>(
+      g, Route{PATH_G8, false, false, g8_plan<true>(M, N, K, ws, ws_bytes), group_m(N), 0});
 }
 
 int lc_gemm_set_tile(int tile) {
@@ -2495,16 +2437,7 @@ int lc_gemm_tn_ws(hipStream_t stream, int M, int N1, int N2, const void* A, long
     plan_tn(p, p.n_tiles);
     if (wide && ws_bytes >= LC_SPLITK_TICKET_BYTES + (long)p.wgs * tn_pslot(p.pw) * 4)
       p.part = reinterpret_cast<float*>(static_cast<char*>(ws) + LC_SPLITK_TICKET_BYTES);
-    TnProb none{};
-    if (p.pw == 256)
-      hipLaunchKernelGGL(gemm_tn_wide_kernel<256>, dim3(p.wgs), dim3(512), 0, stream, p, none);
-    else
-      hipLaunchKernelGGL(gemm_tn_wide_kernel<128>, dim3(p.wgs), dim3(512), 0, stream, p, none);
-    if (p.part) {
-      const int outs = p.Nw * 64 + p.Nw + 64;
-      hipLaunchKernelGGL(tn_reduce_kernel, dim3((outs + 255) / 256), dim3(256), 0, stream, p, none);
-    }
-    LC_LAUNCH_RET();
+    return launch_tn_wide(stream, p, TnProb{});
   }
   const int tiles = ((N1 + 63) / 64) * ((N2 + 63) / 64);
   // Enough M-chunks to give ~4 workgroups per CU, each chunk a multiple of 64 rows.
@@ -2584,17 +2517,7 @@ static int adapter_wgrad(hipStream_t stream, int M, int D, const void* gout, lon
     up.part = reinterpret_cast<float*>(static_cast<char*>(ws) + LC_SPLITK_TICKET_BYTES);
     down.part = up.part + (long)up.wgs * tn_pslot(pw);
   }
-  if (pw == 256)
-    hipLaunchKernelGGL(gemm_tn_wide_kernel<256>, dim3(up.wgs + down.wgs), dim3(512), 0, stream, up,
-                       down);
-  else
-    hipLaunchKernelGGL(gemm_tn_wide_kernel<128>, dim3(up.wgs + down.wgs), dim3(512), 0, stream, up,
-                       down);
-  if (up.part) {
-    const int outs = 2 * (D * 64 + D + 64);
-    hipLaunchKernelGGL(tn_reduce_kernel, dim3((outs + 255) / 256), dim3(256), 0, stream, up, down);
-  }
-  LC_LAUNCH_RET();
+  return launch_tn_wide(stream, up, down);
 }
 
 int lc_adapter_wgrad_ws(hipStream_t stream, int M, int D, const void* gout, long ldg,

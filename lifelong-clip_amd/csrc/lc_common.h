@@ -332,11 +332,56 @@ LC_DEV void lds_barrier() {
   asm volatile("" ::: "memory");
 }
 
-// Internal launcher shared by the GEMM-shaped fused kernels (gemm.hip).
-int lc_gemm_nt_ex(hipStream_t stream, int epi, int M, int N, int K, const void* A, long lda,
-                  const void* B, long ldb, const float* bias, float alpha, void* out0, long ldo0,
-                  void* out1, long ldo1, const void* aux, long ldaux, const EpiParams& ep,
-                  void* ws = nullptr, long ws_bytes = 0);
+// Epilogues of the NT GEMMs (lc_gemm_nt's epi; 8-11 internal to the adapter entry points).
+enum {
+  EPI_BF16 = 0,        // out0 bf16 = acc*alpha + bias
+  EPI_F32 = 1,         // out0 f32  = acc*alpha + bias
+  EPI_RESID = 2,       // out0 f32  = aux_f32 + acc*alpha + bias          (residual add)
+  EPI_GELU = 3,        // out0 bf16 = pre = acc+bias ; out1 bf16 = quick_gelu(pre)
+  EPI_GELU_BWD = 4,    // out0 bf16 = (acc*alpha) * quick_gelu'(aux_bf16)
+  EPI_BF16_F32 = 5,    // out0 bf16 and out1 f32 of acc*alpha + bias
+  EPI_GELU_D = 6,      // out0 bf16 = quick_gelu'(pre) ; out1 bf16 = quick_gelu(pre), pre = acc+bias
+  EPI_MUL = 7,         // out0 bf16 = (acc*alpha) * aux_bf16
+  // fused adapter epilogues (internal; adapter.py:59-72 as two skinny GEMMs)
+  EPI_AD_DOWN = 8,     // out0 bf16 = relu(acc + bias) * dropmask(seed, m, n) / keep
+  EPI_AD_UP = 9,       // out0 f32 = aux_f32 + aux2_bf16 + scale * (acc + bias)
+  EPI_AD_MASK = 10,    // out0 bf16 = aux_bf16 > 0 ? alpha * acc / keep : 0
+  EPI_AD_ADD = 11,     // out0 bf16 = aux_bf16 + acc
+  // fp8-output epilogues of the fp8 GEMM (MaPLe's fp8 mode): out1 = e4m3 codes (ldo1 in bytes)
+  // + E8M0 scales (ep.q_scale, ep.q_rows) of the bf16-rounded value, bit-identical to the bf16
+  // epilogue followed by quant_fp8 (quant.hip) — the next fp8 GEMM's A operand straight from here
+  EPI_GELU_D_Q8 = 12,  // out0 bf16 = quick_gelu'(pre) ; out1 fp8 = quick_gelu(pre), pre = acc+bias
+  EPI_MUL_Q8 = 13,     // out1 fp8 = (acc*alpha) * aux_bf16 (out0 unused)
+  // the half residual stream (lc_common.h xres): out0 half = aux_half + acc*alpha + bias
+  EPI_RESID16 = 14,
+};
+
+// One NT GEMM launch: C[M,N] = A[M,K] . B[N,K]^T with epilogue epi (include/lc_clip.h has the
+// operands' contract). The extern "C" entry points fill it; the router and the launchers of
+// gemm.hip read it. lda / ldb in elements (fp8: bytes); ws: split-K workspace or nullptr.
+struct GemmArgs {
+  hipStream_t stream;
+  int epi, M, N, K;
+  const void* A;
+  long lda;
+  const void* B;
+  long ldb;
+  const float* bias;
+  float alpha;
+  void* out0;
+  long ldo0;
+  void* out1;
+  long ldo1;
+  const void* aux;
+  long ldaux;
+  EpiParams ep;
+  void* ws = nullptr;
+  long ws_bytes = 0;
+  Fp8Scales sc = {};  // fp8 operands only
+};
+
+// Internal launcher shared by the GEMM-shaped fused kernels (gemm.hip): validate, route, launch.
+int lc_gemm_nt_ex(const GemmArgs& g);
 
 // hipBLASLt for plain bf16 GEMMs that the step routes there (blaslt.hip, bf16 build only):
 // C[M, N] = A[M, K] . B[N, K]^T, false when hipBLASLt cannot take the launch (nothing written)

@@ -1413,11 +1413,11 @@ static int adapter_fwd(hipStream_t st, int M, int D, const void* z, long ldz, co
   EpiParams ep{z, ldz, scale, keep, (uint64_t)seed, nullptr, seed_dev};
   ep.row_mul = row_mul;
   ep.row_add = row_add;
-  int rc = lc_gemm_nt_ex(st, 8 /*EPI_AD_DOWN*/, M, AD_H, D, z, ldz, Wd, D, bd, 1.0f, hout, AD_H,
-                         nullptr, 0, nullptr, 0, ep);
+  int rc = lc_gemm_nt_ex({st, EPI_AD_DOWN, M, AD_H, D, z, ldz, Wd, D, bd, 1.0f, hout, AD_H,
+                          nullptr, 0, nullptr, 0, ep});
   if (rc) return rc;
-  return lc_gemm_nt_ex(st, 9 /*EPI_AD_UP*/, M, D, AD_H, hout, AD_H, Wu, AD_H, bu, 1.0f, xout, ldx,
-                       nullptr, 0, resid, ldx, ep);
+  return lc_gemm_nt_ex({st, EPI_AD_UP, M, D, AD_H, hout, AD_H, Wu, AD_H, bu, 1.0f, xout, ldx,
+                        nullptr, 0, resid, ldx, ep});
 }
 
 int lc_adapter_fwd(hipStream_t st, int M, int D, const void* z, long ldz, const void* Wd,
@@ -1592,12 +1592,12 @@ int lc_adapter_bwd(hipStream_t st, int M, int D, const void* gout, long ldg, con
     LC_LAUNCH_RET();
   }
   EpiParams ep{nullptr, 0, scale, keep, 0, nullptr};
-  int rc = lc_gemm_nt_ex(st, 10 /*EPI_AD_MASK*/, M, AD_H, D, gout, ldg, WuT, D, nullptr, scale, dpre,
-                         AD_H, nullptr, 0, h, AD_H, ep);
+  int rc = lc_gemm_nt_ex({st, EPI_AD_MASK, M, AD_H, D, gout, ldg, WuT, D, nullptr, scale, dpre,
+                          AD_H, nullptr, 0, h, AD_H, ep});
   if (rc) return rc;
   if (dz == nullptr) return LC_OK;  // dpre only (the input gradient is not needed)
-  return lc_gemm_nt_ex(st, 11 /*EPI_AD_ADD*/, M, D, AD_H, dpre, AD_H, WdT, AD_H, nullptr, 1.0f, dz,
-                       ldz, nullptr, 0, gout, ldg, ep);
+  return lc_gemm_nt_ex({st, EPI_AD_ADD, M, D, AD_H, dpre, AD_H, WdT, AD_H, nullptr, 1.0f, dz,
+                        ldz, nullptr, 0, gout, ldg, ep});
 }
 
 int lc_check_finite(hipStream_t st, long n, const float* g, int* flag) {
