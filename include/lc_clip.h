@@ -612,6 +612,10 @@ int lc_gemm_tn_f16(hipStream_t stream, int M, int N1, int N2, const void* A, lon
 int lc_gemm_tn_ws_f16(hipStream_t stream, int M, int N1, int N2, const void* A, long lda,
                       const void* B, long ldb, float alpha, float* C, long ldc, float* colsum,
                       float colsum_scale, void* ws, long ws_bytes);
+/* (the half build keeps its own tile override and stream-K mode: lc_gemm_set_tile /
+ * lc_gemm_set_streamk do not reach lc_gemm_nt_f16) */
+int lc_gemm_set_tile_f16(int tile);
+int lc_gemm_set_streamk_f16(int mode);
 int lc_layernorm_fwd_f16(hipStream_t stream, int rows, int D, const float* x, long ldx,
                          const int* row_idx, const float* gamma, const float* beta, void* y,
                          int y_f32, long ldy, float* mean, float* rstd);

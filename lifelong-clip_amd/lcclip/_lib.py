@@ -111,6 +111,7 @@ SIGNATURES = {
 
 # the IEEE-half (text tower) forms: same arguments (include/lc_clip.h, "IEEE-half storage")
 F16_ENTRY_POINTS = ("lc_gemm_nt", "lc_gemm_nt_ws", "lc_gemm_nt_rows", "lc_gemm_tn", "lc_gemm_tn_ws",
+                    "lc_gemm_set_tile", "lc_gemm_set_streamk",
                     "lc_layernorm_fwd", "lc_layernorm_bwd", "lc_attn_fwd", "lc_attn_bwd",
                     "lc_attn_bwd_set_form", "lc_attn_row_fwd", "lc_attn_row_bwd",
                     "lc_attn_bwd_live_row",
