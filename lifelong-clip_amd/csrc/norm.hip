@@ -160,7 +160,11 @@ ln_fwd_kernel(int rows, const XT* __restrict__ x, long ldx, const int* __restric
   float s = 0.f;
 #pragma unroll
   for (int i = 0; i < V; ++i) s += v[i];
-  const float mean = wave_sum(s) * (1.0f / D);
+  float mean = wave_sum(s) * (1.0f / D);
+  // the deviations are taken about the mean that is saved (and that ln_bwd_kernel reads back):
+  // left to the compiler, x - sum * (1 / D) becomes one fma on the unrounded product, which for
+  // D = 768 (1 / D is not a power of two) is another mean, and a constant row got y != beta
+  asm volatile("" : "+v"(mean));
   float q = 0.f;
 #pragma unroll
   for (int i = 0; i < V; ++i) {
