@@ -295,6 +295,9 @@ int lc_eot_rows(hipStream_t stream, int C, int L, const int64_t* tokens, int* ro
  * q|k|v at columns 0, H*64, 2*H*64; O [n_seq*L, ldo]; lse f32 [n_seq*H, L] (log2 domain).
  * ldq, ldo, lddq % 8 == 0; O and dqkv 16-B aligned (each row's 64 head columns are written as
  * 16-B pieces).
+ * Every row stride of every attention entry point below is under 2^23 bytes: ldq, ldo, lddq
+ * < 2^22 elements, the fp8 form's lddq (bytes) < 2^23. The kernels address a sequence's rows, up
+ * to row 255 of its padded chunks, with 32-bit byte offsets; LC_EINVAL otherwise.
  * causal = 1 applies the text tower's upper-triangular -inf mask.
  * Replaces: lora.py:950-1071 (q scaling, bmm, mask, softmax, dropout p=0, bmm) and the SDPA
  * path of torch nn.MultiheadAttention (model.py:217,230), forward and backward. */

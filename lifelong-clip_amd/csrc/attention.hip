@@ -62,6 +62,14 @@ LC_DEV bf16x8 pack8(const f32x4& a, const f32x4& b) {
   return as_bf8(u32x4{pack2bf(a[0], a[1]), pack2bf(a[2], a[3]), pack2bf(b[0], b[1]), pack2bf(b[2], b[3])});
 }
 
+// sum over the 8 lanes of a row (all of them get it)
+LC_DEV float sum_row8(float v) {
+  v += __shfl_xor(v, 1);
+  v += __shfl_xor(v, 2);
+  v += __shfl_xor(v, 4);
+  return v;
+}
+
 // q / k / v, O and dO rows are read once per (sequence, head): nontemporal (step +0.4 %,
 // profiles/r02/epilogue_knockout.txt)
 LC_DEV uint4 ld16_or_zero(const bf16_t* p, bool ok) {
@@ -85,6 +93,9 @@ LC_DEV uint4 seq_ld16(__amdgpu_buffer_rsrc_t r, int off) {  // nontemporal (read
   const auto v = __builtin_amdgcn_raw_buffer_load_b128(r, off, 0, 2);
   return make_uint4(v[0], v[1], v[2], v[3]);
 }
+// a buffer offset past every descriptor: the load reads zero (the host's check() keeps every
+// offset into a sequence's rows, and every descriptor's size, below it)
+constexpr int OOR = 0x7ffffff0;
 
 // Lane offsets (bytes) into a swizzled 128-B-row image, valid for any row block that starts at a
 // multiple of 16 rows:
@@ -366,9 +377,7 @@ attn_bwd_kv_kernel(int L, int H, int D, const bf16_t* __restrict__ qkv, long ldq
 #pragma unroll
     for (int k = 0; k < 4; ++k)
       dsum += bf2f(aa[k] & 0xffff) * bf2f(bb[k] & 0xffff) + bf2f(aa[k] >> 16) * bf2f(bb[k] >> 16);
-    dsum += __shfl_xor(dsum, 1);
-    dsum += __shfl_xor(dsum, 2);
-    dsum += __shfl_xor(dsum, 4);
+    dsum = sum_row8(dsum);
     if (ch == 0) {
       nd_s[r] = -dsum;
       nlse_s[r] = r < L ? -lv[i] : -1e30f;
@@ -523,7 +532,6 @@ attn_bwd_kernel(int n_items, int L, int H, int D, const bf16_t* __restrict__ qkv
   const int rowc = row >> 5;
   constexpr bool KSLOT8 = ROW && NQB == 8;
   constexpr int R_MUL = KSLOT8 ? 4 : 8, R_STEP = KSLOT8 ? 16 : 4;
-  constexpr int OOR = 0x7ffffff0;  // a buffer offset past every descriptor: the load reads zero
   __shared__ __attribute__((aligned(16))) char smem[Lay::BYTES];
   char* Qs = smem + Lay::Q_OFF;
   char* dOs = smem + Lay::DO_OFF;
@@ -1115,23 +1123,12 @@ attn_bwd2_kernel(int L, int H, int D, const bf16_t* __restrict__ qkv, long ldq,
   // >= L read zeros from the range check: no branch around a load, so no vmcnt(0) between them):
   // K / V rows for the images, then the wave's two query blocks' Q / dO fragments (B operands
   // of S^T / dP^T: lane holds row q = qb + t, columns s*32 + 8g ..), O rows and lse
-  auto rows_rsrc = [&](const void* p, long row0, long row_bytes) {
-    const uint64_t a = (uint64_t)(static_cast<const char*>(p) + row0 * row_bytes);
-    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)a);
-    const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)(a >> 32));
-    const int nb = __builtin_amdgcn_readfirstlane((int)(L * row_bytes));
-    return __builtin_amdgcn_make_buffer_rsrc((void*)(((uint64_t)hi << 32) | lo), 0, nb, 0x00020000);
-  };
-  auto bld16 = [](__amdgpu_buffer_rsrc_t r, int off) {  // nontemporal (read once)
-    const auto v = __builtin_amdgcn_raw_buffer_load_b128(r, off, 0, 2);
-    return make_uint4(v[0], v[1], v[2], v[3]);
-  };
   const long lb = (ko & 8) ? 0 : base;
   const int hl = (ko & 8) ? 0 : h;
-  const auto rq = rows_rsrc(qkv, lb, ldq * 2);
-  const auto rd = rows_rsrc(dO, lb, ldo * 2);
-  const auto rO = rows_rsrc(O, lb, ldo * 2);
-  const auto rl = rows_rsrc(lse, (ko & 8) ? 0 : (long)nh * L, 4);
+  const auto rq = seq_rsrc(qkv, lb, ldq * 2, L);
+  const auto rd = seq_rsrc(dO, lb, ldo * 2, L);
+  const auto rO = seq_rsrc(O, lb, ldo * 2, L);
+  const auto rl = seq_rsrc(lse, (ko & 8) ? 0 : (long)nh * L, 4, L);
   constexpr int IT = LP * 8 / NTH;  // = 4
   const int ch = tid & 7;
   uint4 kv[IT], vv[IT];
@@ -1139,8 +1136,8 @@ attn_bwd2_kernel(int L, int H, int D, const bf16_t* __restrict__ qkv, long ldq,
   for (int i = 0; i < IT; ++i) {
     const int r = (tid + i * NTH) >> 3;
     const int off = r * (int)ldq * 2 + (hl * 64 + ch * 8) * 2;
-    kv[i] = bld16(rq, off + D * 2);
-    vv[i] = bld16(rq, off + D * 4);
+    kv[i] = seq_ld16(rq, off + D * 2);
+    vv[i] = seq_ld16(rq, off + D * 4);
   }
   bf16x8 qf[2][2], df[2][2];
   uint4 of[2][2];
@@ -1151,9 +1148,9 @@ attn_bwd2_kernel(int L, int H, int D, const bf16_t* __restrict__ qkv, long ldq,
 #pragma unroll
     for (int s = 0; s < 2; ++s) {
       const int cb = (hl * 64 + s * 32 + g * 8) * 2;
-      uint4 u = bld16(rq, q * (int)ldq * 2 + cb);
-      uint4 d = bld16(rd, q * (int)ldo * 2 + cb);
-      of[bk][s] = bld16(rO, q * (int)ldo * 2 + cb);
+      uint4 u = seq_ld16(rq, q * (int)ldq * 2 + cb);
+      uint4 d = seq_ld16(rd, q * (int)ldo * 2 + cb);
+      of[bk][s] = seq_ld16(rO, q * (int)ldo * 2 + cb);
       qf[bk][s] = *reinterpret_cast<bf16x8*>(&u);
       df[bk][s] = *reinterpret_cast<bf16x8*>(&d);
     }
@@ -1379,13 +1376,7 @@ LC_DEV float dot8(const float (&a)[8], const float (&b)[8]) {
   for (int j = 0; j < 8; ++j) s = __builtin_fmaf(a[j], b[j], s);
   return s;
 }
-// sum over the 8 lanes of a row (all of them get it) / over the 8 rows of a wave's pass
-LC_DEV float sum_row8(float v) {
-  v += __shfl_xor(v, 1);
-  v += __shfl_xor(v, 2);
-  v += __shfl_xor(v, 4);
-  return v;
-}
+// sum over the 8 rows of a wave's pass
 LC_DEV float sum_rows8(float v) {
   v += __shfl_xor(v, 8);
   v += __shfl_xor(v, 16);
@@ -1475,30 +1466,68 @@ attn_row_bwd_kernel(int L, int H, int D, const bf16_t* __restrict__ qkv, long ld
   }
 }
 
-// workgroups of a persistent launch: as many as fit on the chip at once (LDS-limited) when there
-// are many items per workgroup (L = 197: 3072 items, 12 per workgroup), else one per item
-int persistent_grid(int items, int lds_bytes) {
-  static int cus = 0;
-  if (!cus) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-        cus <= 0)
-      cus = 256;
-  }
-  int per_cu = (160 * 1024) / lds_bytes;
-  per_cu = per_cu < 1 ? 1 : (per_cu > 4 ? 4 : per_cu);
-  const int g = cus * per_cu;
-  // a few items per workgroup would leave a ragged last round: one item each (no pipelining)
-  return items < 4 * g ? items : g;
-}
+// --------------------------------------------------------------------------------- host side
+// One attention launch (include/lc_clip.h has the operands' contract). The extern "C" entry
+// points fill it, casts done there; check(), route() and the family launchers read it.
+enum Entry { E_FWD, E_ROW_FWD, E_BWD, E_FP8, E_LIVE_ROW, E_ROW_BWD };
+struct AttnArgs {
+  hipStream_t stream;
+  int n_seq, L, H, causal;
+  const bf16_t* qkv;
+  long ldq;
+  const bf16_t* O;  // O and lse: the forward's outputs (its entry points take them non-const)
+  long ldo;
+  const float* lse;
+  const bf16_t* dO = nullptr;  // from here on the backward's
+  bf16_t* dqkv = nullptr;
+  long lddq = 0;               // elements; bytes in the fp8 form
+  int row = -1;                // the one-row forms' query row: O / dO / lse are compact then
+  uint8_t* q_scale = nullptr;  // the fp8 form's E8M0 scales
+  long q_rows = 0;
+  int D() const { return H * 64; }
+  int nqb() const { return (L + 31) / 32; }
+  int items() const { return n_seq * H; }
+};
 
-bool attn_fwd_online() {  // DIAG builds: LCCLIP_ATTN_FWD_ONLINE=0 selects the two-pass forward
-  static const bool online = [] {
-    const char* e = lc_diag_env("LCCLIP_ATTN_FWD_ONLINE");
-    return !(e && e[0] == '0');
-  }();
-  return online;
+constexpr float ATTN_SCALE = 0.125f;  // 64^-0.5
+// 32-row chunks a kernel family takes: 8 (L <= 256), but 7 for the fused kernel's full and fp8
+// modes and the two-phase kernel, which hold every chunk in LDS (BwdLds<8> does not fit, so
+// attn_bwd_kernel<8> without ROW must not be instantiated)
+constexpr int MAX_CHUNKS = 8, FUSED_MAX_CHUNKS = 7;
+
+// 32-bit offsets. The kernels reach a sequence's rows through a raw-buffer descriptor and an int
+// byte offset r * (int)ld * 2 + column bytes. r runs over the PADDED rows, up to 32 * NQB - 1
+// <= 255 (attn_row_bwd_kernel: 255 whatever L is), and the column bytes end at 3 * D * 2 at the
+// most (v of the last head: the k | v column offset included), within one row's bytes. So every
+// offset formed, attn_row_bwd_kernel's `oob` and every descriptor's size (L rows) is at most
+// 256 * row bytes. Row bytes are a multiple of 16: below 2^23 they are <= 2^23 - 16, and 256 of
+// them <= 2^31 - 4096, which fits an int and stays below OOR. One bound on the strides alone
+// then (ld < 2^22 elements; the fp8 form's lddq, in bytes, < 2^23), the same in all six launches.
+constexpr long MAX_ROW_BYTES = 1L << 23;
+static_assert(32 * MAX_CHUNKS * (MAX_ROW_BYTES - 16) < OOR && ROW_IT <= MAX_CHUNKS, "see above");
+bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
+// The one argument check: which fields entry point e has, and which limits apply to it.
+int check(const AttnArgs& a, Entry e) {
+  const bool fwd = e == E_FWD || e == E_ROW_FWD, fp8 = e == E_FP8;
+  const bool row_pair = e == E_ROW_FWD || e == E_ROW_BWD, one_row = row_pair || e == E_LIVE_ROW;
+  const int max_L = 32 * (fp8 ? FUSED_MAX_CHUNKS : row_pair ? ROW_IT : MAX_CHUNKS);
+  LC_CHECK_ARG(a.n_seq > 0 && a.L > 0 && a.L <= max_L && a.H > 0);
+  LC_CHECK_ARG(one_row == (a.row >= 0) && a.row < a.L);
+  const long D = a.D(), es = fp8 ? 1 : 2;  // es: bytes per dqkv element
+  LC_CHECK_ARG(a.ldq >= 3 * D && a.ldq % 8 == 0 && a.ldo >= D && a.ldo % 8 == 0);
+  // rows moved as 16-B pieces by pointer: the forward's O, the compact O / dO rows, dqkv
+  LC_CHECK_ARG(!(fwd || one_row) || aligned16(a.O));
+  if (!fwd) {
+    LC_CHECK_ARG(!one_row || aligned16(a.dO));
+    LC_CHECK_ARG(a.lddq >= 3 * D && a.lddq % (16 / es) == 0 && aligned16(a.dqkv));
+  }
+  if (fp8)
+    LC_CHECK_ARG(a.q_scale != nullptr && a.q_rows % 256 == 0 &&
+                 a.q_rows >= ((long)a.n_seq * a.L + 255) / 256 * 256);
+  LC_CHECK_ARG(a.ldq < MAX_ROW_BYTES / 2 && a.ldo < MAX_ROW_BYTES / 2 &&
+               a.lddq < MAX_ROW_BYTES / es);
+  return LC_OK;
 }
 
 // lc_attn_bwd_set_form: 0 automatic, else one of these
@@ -1513,6 +1542,129 @@ int g_attn_bwd_form = [] {  // DIAG builds: LC_ATTN_BWD_FORM=<form>, LC_ATTN_BWD
   const char* e = lc_diag_env("LC_ATTN_BWD_SPLIT");
   return e && atoi(e) ? (int)ATTN_BWD_SPLIT : 0;
 }();
+const bool g_fwd_online = [] {  // DIAG builds: LCCLIP_ATTN_FWD_ONLINE=0: the two-pass forward
+  const char* e = lc_diag_env("LCCLIP_ATTN_FWD_ONLINE");
+  return !(e && e[0] == '0');
+}();
+
+// The kernel family a checked launch runs on, decided here and nowhere else (table: DESIGN.md).
+enum Family { F_REFUSE, F_FORWARD, F_FUSED, F_SPLIT, F_TWO_PHASE, F_ROW_VALU };
+Family route(Entry e, int nqb, int form) {
+  switch (e) {
+    case E_FWD: case E_ROW_FWD: return F_FORWARD;
+    case E_ROW_BWD: return F_ROW_VALU;
+    case E_FP8: return F_FUSED;
+    // the result is the default form's (fused kernel; key-major + query-major pair at 8 chunks)
+    case E_LIVE_ROW: return form == 0 || form == ATTN_BWD_FUSED ? F_FUSED : F_REFUSE;
+    case E_BWD: break;
+  }
+  // fused single-pass kernel (dS^T parked in LDS, 1 workgroup per CU) up to 224 keys; the split
+  // key-major + query-major pair beyond that (LDS); lc_attn_bwd_set_form selects another form
+  if (nqb > FUSED_MAX_CHUNKS || form == ATTN_BWD_SPLIT) return F_SPLIT;
+  return form == ATTN_BWD_TWO_PHASE ? F_TWO_PHASE : F_FUSED;
+}
+
+// f(std::integral_constant<int, nqb>) for nqb in 1..MAX (the family's chunk limit: nothing
+// beyond it is instantiated), LC_EINVAL outside; f(std::true_type / std::false_type) for a flag
+template <int MAX, class F>
+int with_chunks(int nqb, const F& f) {
+  if constexpr (MAX == 0) return LC_EINVAL;
+  else return nqb == MAX ? f(std::integral_constant<int, MAX>{}) : with_chunks<MAX - 1>(nqb, f);
+}
+template <class F>
+int with_flag(bool flag, const F& f) {
+  return flag ? f(std::true_type{}) : f(std::false_type{});
+}
+
+// workgroups of a persistent launch: as many as fit on the chip at once (LDS-limited) when there
+// are many items per workgroup (L = 197: 3072 items, 12 per workgroup), else one per item
+int persistent_grid(int items, int lds_bytes) {
+  int per_cu = (160 * 1024) / lds_bytes;
+  per_cu = per_cu < 1 ? 1 : (per_cu > 4 ? 4 : per_cu);
+  const int g = cu_count() * per_cu;
+  // a few items per workgroup would leave a ragged last round: one item each (no pipelining)
+  return items < 4 * g ? items : g;
+}
+
+int launch_fwd(const AttnArgs& a) {
+  return with_chunks<MAX_CHUNKS>(a.nqb(), [&](auto Q) {
+    return with_flag(g_fwd_online, [&](auto ONLINE) {
+      return with_flag(a.row >= 0, [&](auto ROW) -> int {
+        constexpr int NQB = decltype(Q)::value;
+        hipLaunchKernelGGL((attn_fwd_kernel<NQB, decltype(ONLINE)::value, decltype(ROW)::value>),
+                           dim3(a.items()), dim3(64 * NQB), 0, a.stream, a.L, a.H, a.D(), a.qkv,
+                           a.ldq, const_cast<bf16_t*>(a.O), a.ldo, const_cast<float*>(a.lse),
+                           a.causal, ATTN_SCALE, a.row >= 0 ? a.row : 0);
+        LC_LAUNCH_RET();
+      });
+    });
+  });
+}
+
+// full (Q8 = ROW = false), fp8 outputs (Q8) or the one-row mode (ROW: q_rows carries the row).
+// The grid rule, once: persistent from 5 chunks (the kernel's PERSIST), else a workgroup per item.
+template <bool Q8, bool ROW>
+int launch_fused(const AttnArgs& a) {
+  return with_chunks<ROW ? MAX_CHUNKS : FUSED_MAX_CHUNKS>(a.nqb(), [&](auto Q) -> int {
+    constexpr int NQB = decltype(Q)::value;
+    using Lay = typename std::conditional<ROW, BwdLdsRow<NQB>, BwdLds<NQB>>::type;
+    const int grid = NQB >= 5 ? persistent_grid(a.items(), Lay::BYTES) : a.items();
+    hipLaunchKernelGGL((attn_bwd_kernel<NQB, (NQB >= 5), Q8, ROW>), dim3(grid), dim3(64 * NQB), 0,
+                       a.stream, a.items(), a.L, a.H, a.D(), a.qkv, a.ldq, a.O, a.dO, a.ldo, a.lse,
+                       a.dqkv, a.lddq, a.causal, ATTN_SCALE, a.q_scale,
+                       ROW ? (long)a.row : a.q_rows);
+    LC_LAUNCH_RET();
+  });
+}
+
+int launch_split(const AttnArgs& a) {  // key-major (dK, dV), then query-major (dQ)
+  return with_chunks<MAX_CHUNKS>(a.nqb(), [&](auto Q) -> int {
+    constexpr int NQB = decltype(Q)::value;
+    auto launch = [&](auto kern) {
+      hipLaunchKernelGGL(kern, dim3(a.items()), dim3(64 * NQB), 0, a.stream, a.L, a.H, a.D(),
+                         a.qkv, a.ldq, a.O, a.dO, a.ldo, a.lse, a.dqkv, a.lddq, a.causal,
+                         ATTN_SCALE);
+    };
+    launch(attn_bwd_kv_kernel<NQB>);
+    launch(attn_bwd_q_kernel<NQB>);
+    LC_LAUNCH_RET();
+  });
+}
+
+int launch_two_phase(const AttnArgs& a) {
+  return with_chunks<FUSED_MAX_CHUNKS>(a.nqb(), [&](auto Q) {
+    return with_flag(a.causal != 0, [&](auto CAUSAL) -> int {
+      constexpr int NQB = decltype(Q)::value;
+      hipLaunchKernelGGL((attn_bwd2_kernel<NQB, decltype(CAUSAL)::value>), dim3(a.items()),
+                         dim3(64 * NQB), 0, a.stream, a.L, a.H, a.D(), a.qkv, a.ldq, a.O, a.dO,
+                         a.ldo, a.lse, a.dqkv, a.lddq, ATTN_SCALE, g_att2_ko);
+      LC_LAUNCH_RET();
+    });
+  });
+}
+
+int launch_row_valu(const AttnArgs& a) {
+  hipLaunchKernelGGL(attn_row_bwd_kernel, dim3(a.items()), dim3(ROW_NTH), 0, a.stream, a.L, a.H,
+                     a.D(), a.qkv, a.ldq, a.row, a.O, a.dO, a.ldo, a.lse, a.dqkv, a.lddq, a.causal,
+                     ATTN_SCALE);
+  LC_LAUNCH_RET();
+}
+
+// Every launching entry point: check, route, launch on the family the route names.
+int run(Entry e, const AttnArgs& a) {
+  if (const int rc = check(a, e)) return rc;
+  switch (route(e, a.nqb(), g_attn_bwd_form)) {
+    case F_FORWARD: return launch_fwd(a);
+    case F_FUSED:
+      return a.q_scale   ? launch_fused<true, false>(a)
+             : a.row >= 0 ? launch_fused<false, true>(a) : launch_fused<false, false>(a);
+    case F_SPLIT: return launch_split(a);
+    case F_TWO_PHASE: return launch_two_phase(a);
+    case F_ROW_VALU: return launch_row_valu(a);
+    case F_REFUSE: break;
+  }
+  return LC_EUNSUPPORTED;
+}
 
 }  // namespace
 
@@ -1520,55 +1672,15 @@ extern "C" {
 
 int lc_attn_fwd(hipStream_t st, int n_seq, int L, int H, const void* qkv, long ldq, void* O,
                 long ldo, float* lse, int causal) {
-  LC_CHECK_ARG(n_seq > 0 && L > 0 && L <= 256 && H > 0 && ldq >= 3 * H * 64 && ldo >= H * 64);
-  LC_CHECK_ARG(ldq % 8 == 0 && ldo % 8 == 0 && ((uintptr_t)O & 15) == 0);  // 16-B row stores
-  const int D = H * 64;
-  const int nqb = (L + 31) / 32;
-  dim3 grid(n_seq * H);
-  const float scale = 0.125f;  // 64^-0.5
-  const bool online = attn_fwd_online();
-  switch (nqb) {
-#define LC_AF(Q)                                                                                \
-  case Q:                                                                                      \
-    if (online)                                                                                \
-      hipLaunchKernelGGL((attn_fwd_kernel<Q, true>), grid, dim3(64 * Q), 0, st, L, H, D,       \
-                         (const bf16_t*)qkv, ldq, (bf16_t*)O, ldo, lse, causal, scale);        \
-    else                                                                                       \
-      hipLaunchKernelGGL((attn_fwd_kernel<Q, false>), grid, dim3(64 * Q), 0, st, L, H, D,      \
-                         (const bf16_t*)qkv, ldq, (bf16_t*)O, ldo, lse, causal, scale);        \
-    break;
-    LC_AF(1) LC_AF(2) LC_AF(3) LC_AF(4) LC_AF(5) LC_AF(6) LC_AF(7) LC_AF(8)
-#undef LC_AF
-    default:
-      return LC_EINVAL;
-  }
-  LC_LAUNCH_RET();
+  return run(E_FWD, {st, n_seq, L, H, causal, (const bf16_t*)qkv, ldq, (const bf16_t*)O, ldo,
+                     lse});
 }
 
 int lc_attn_bwd_fp8(hipStream_t st, int n_seq, int L, int H, const void* qkv, long ldq,
                     const void* O, const void* dO, long ldo, const float* lse, void* dqkv, long lddq,
                     void* q_scale, long q_rows, int causal) {
-  LC_CHECK_ARG(n_seq > 0 && L > 0 && L <= 224 && H > 0 && ldq >= 3 * H * 64 && ldo >= H * 64);
-  LC_CHECK_ARG(lddq >= 3 * H * 64 && lddq % 16 == 0 && ((uintptr_t)dqkv & 15) == 0 &&
-               ldq % 8 == 0 && ldo % 8 == 0 && q_scale != nullptr && q_rows % 256 == 0 &&
-               q_rows >= ((long)n_seq * L + 255) / 256 * 256);
-  const int D = H * 64;
-  const float scale = 0.125f;
-  switch ((L + 31) / 32) {
-#define LC_ABQ(Q)                                                                               \
-  case Q:                                                                                      \
-    hipLaunchKernelGGL((attn_bwd_kernel<Q, (Q >= 5), true>),                                   \
-                       dim3(Q >= 5 ? persistent_grid(n_seq * H, BwdLds<Q>::BYTES) : n_seq * H),  \
-                       dim3(64 * Q), 0, st, n_seq * H, L, H, D, (const bf16_t*)qkv, ldq,        \
-                       (const bf16_t*)O, (const bf16_t*)dO, ldo, lse, (bf16_t*)dqkv, lddq,      \
-                       causal, scale, (uint8_t*)q_scale, q_rows);                               \
-    break;
-    LC_ABQ(1) LC_ABQ(2) LC_ABQ(3) LC_ABQ(4) LC_ABQ(5) LC_ABQ(6) LC_ABQ(7)
-#undef LC_ABQ
-    default:
-      return LC_EINVAL;
-  }
-  LC_LAUNCH_RET();
+  return run(E_FP8, {st, n_seq, L, H, causal, (const bf16_t*)qkv, ldq, (const bf16_t*)O, ldo, lse,
+                     (const bf16_t*)dO, (bf16_t*)dqkv, lddq, -1, (uint8_t*)q_scale, q_rows});
 }
 
 int lc_attn_bwd_set_form(int form) {
@@ -1579,142 +1691,29 @@ int lc_attn_bwd_set_form(int form) {
 
 int lc_attn_bwd(hipStream_t st, int n_seq, int L, int H, const void* qkv, long ldq, const void* O,
                 const void* dO, long ldo, const float* lse, void* dqkv, long lddq, int causal) {
-  LC_CHECK_ARG(n_seq > 0 && L > 0 && L <= 256 && H > 0 && ldq >= 3 * H * 64 && ldo >= H * 64);
-  LC_CHECK_ARG(lddq >= 3 * H * 64 && ldq % 8 == 0 && ldo % 8 == 0 && lddq % 8 == 0 &&
-               ((uintptr_t)dqkv & 15) == 0);  // 16-B row stores
-  const int D = H * 64;
-  const int nqb = (L + 31) / 32;
-  dim3 grid(n_seq * H);
-  const float scale = 0.125f;
-  // fused single-pass kernel (dS^T parked in LDS, 1 workgroup per CU) up to 224 keys; the split
-  // key-major + query-major pair beyond that (LDS); lc_attn_bwd_set_form selects another form
-  const int form = g_attn_bwd_form ? g_attn_bwd_form : ATTN_BWD_FUSED;
-  const bool split = form == ATTN_BWD_SPLIT;
-  if (form == ATTN_BWD_TWO_PHASE && nqb <= 7) {
-    switch (nqb) {
-#define LC_AB2(Q)                                                                               \
-  case Q:                                                                                      \
-    if (causal)                                                                                \
-      hipLaunchKernelGGL((attn_bwd2_kernel<Q, true>), grid, dim3(64 * Q), 0, st, L, H, D,      \
-                         (const bf16_t*)qkv, ldq, (const bf16_t*)O, (const bf16_t*)dO, ldo,    \
-                         lse, (bf16_t*)dqkv, lddq, scale, g_att2_ko);                          \
-    else                                                                                       \
-      hipLaunchKernelGGL((attn_bwd2_kernel<Q, false>), grid, dim3(64 * Q), 0, st, L, H, D,     \
-                         (const bf16_t*)qkv, ldq, (const bf16_t*)O, (const bf16_t*)dO, ldo,    \
-                         lse, (bf16_t*)dqkv, lddq, scale, g_att2_ko);                          \
-    break;
-      LC_AB2(1) LC_AB2(2) LC_AB2(3) LC_AB2(4) LC_AB2(5) LC_AB2(6) LC_AB2(7)
-#undef LC_AB2
-      default:
-        return LC_EINVAL;
-    }
-    LC_LAUNCH_RET();
-  }
-  if (nqb == 8) {
-    hipLaunchKernelGGL(attn_bwd_kv_kernel<8>, grid, dim3(512), 0, st, L, H, D, (const bf16_t*)qkv,
-                       ldq, (const bf16_t*)O, (const bf16_t*)dO, ldo, lse, (bf16_t*)dqkv, lddq,
-                       causal, scale);
-    hipLaunchKernelGGL(attn_bwd_q_kernel<8>, grid, dim3(512), 0, st, L, H, D, (const bf16_t*)qkv,
-                       ldq, (const bf16_t*)O, (const bf16_t*)dO, ldo, lse, (bf16_t*)dqkv, lddq,
-                       causal, scale);
-    LC_LAUNCH_RET();
-  }
-  switch (nqb) {
-#define LC_AB(Q)                                                                                \
-  case Q:                                                                                      \
-    if (split)                                                                                 \
-      hipLaunchKernelGGL(attn_bwd_kv_kernel<Q>, grid, dim3(64 * Q), 0, st, L, H, D,            \
-                         (const bf16_t*)qkv, ldq, (const bf16_t*)O, (const bf16_t*)dO, ldo,    \
-                         lse, (bf16_t*)dqkv, lddq, causal, scale);                             \
-    if (split)                                                                                 \
-      hipLaunchKernelGGL(attn_bwd_q_kernel<Q>, grid, dim3(64 * Q), 0, st, L, H, D,             \
-                         (const bf16_t*)qkv, ldq, (const bf16_t*)O, (const bf16_t*)dO, ldo,    \
-                         lse, (bf16_t*)dqkv, lddq, causal, scale);                             \
-    else                                                                                       \
-      hipLaunchKernelGGL(attn_bwd_kernel<Q>,                                                   \
-                         dim3(Q >= 5 ? persistent_grid(n_seq * H, BwdLds<Q>::BYTES) : n_seq * H),\
-                         dim3(64 * Q), 0, st, n_seq * H, L, H, D, (const bf16_t*)qkv, ldq,      \
-                         (const bf16_t*)O, (const bf16_t*)dO, ldo, lse, (bf16_t*)dqkv, lddq,    \
-                         causal, scale);                                                       \
-    break;
-    LC_AB(1) LC_AB(2) LC_AB(3) LC_AB(4) LC_AB(5) LC_AB(6) LC_AB(7)
-#undef LC_AB
-    default:
-      return LC_EINVAL;
-  }
-  LC_LAUNCH_RET();
+  return run(E_BWD, {st, n_seq, L, H, causal, (const bf16_t*)qkv, ldq, (const bf16_t*)O, ldo, lse,
+                     (const bf16_t*)dO, (bf16_t*)dqkv, lddq});
 }
 
 int lc_attn_bwd_live_row(hipStream_t st, int n_seq, int L, int H, const void* qkv, long ldq,
                          int row, const void* O_row, const void* dO_row, long ldo,
                          const float* lse_row, void* dqkv, long lddq, int causal) {
-  LC_CHECK_ARG(n_seq > 0 && L > 0 && L <= 256 && H > 0 && row >= 0 && row < L);
-  LC_CHECK_ARG(ldq >= 3 * H * 64 && ldo >= H * 64 && lddq >= 3 * H * 64 && ldq % 8 == 0 &&
-               ldo % 8 == 0 && lddq % 8 == 0 && ((uintptr_t)O_row & 15) == 0 &&
-               ((uintptr_t)dO_row & 15) == 0 && ((uintptr_t)dqkv & 15) == 0 &&
-               (long)L * ldq * 2 < 0x7ffffff0L && (long)L * lddq * 2 < 0x7ffffff0L);
-  // the result is the default form's (fused kernel; key-major + query-major pair at 8 chunks)
-  if (g_attn_bwd_form != 0 && g_attn_bwd_form != ATTN_BWD_FUSED) return LC_EUNSUPPORTED;
-  const int D = H * 64;
-  switch ((L + 31) / 32) {
-#define LC_ABR(Q)                                                                               \
-  case Q:                                                                                      \
-    hipLaunchKernelGGL((attn_bwd_kernel<Q, (Q >= 5), false, true>),                            \
-                       dim3(Q >= 5 ? persistent_grid(n_seq * H, BwdLdsRow<Q>::BYTES)           \
-                                   : n_seq * H),                                               \
-                       dim3(64 * Q), 0, st, n_seq * H, L, H, D, (const bf16_t*)qkv, ldq,       \
-                       (const bf16_t*)O_row, (const bf16_t*)dO_row, ldo, lse_row,              \
-                       (bf16_t*)dqkv, lddq, causal, 0.125f, (uint8_t*)nullptr, (long)row);     \
-    break;
-    LC_ABR(1) LC_ABR(2) LC_ABR(3) LC_ABR(4) LC_ABR(5) LC_ABR(6) LC_ABR(7) LC_ABR(8)
-#undef LC_ABR
-    default:
-      return LC_EINVAL;
-  }
-  LC_LAUNCH_RET();
+  return run(E_LIVE_ROW, {st, n_seq, L, H, causal, (const bf16_t*)qkv, ldq, (const bf16_t*)O_row,
+                          ldo, lse_row, (const bf16_t*)dO_row, (bf16_t*)dqkv, lddq, row});
 }
 
 int lc_attn_row_fwd(hipStream_t st, int n_seq, int L, int H, const void* qkv, long ldq, int row,
                     void* O_row, long ldo, float* lse_row, int causal) {
-  LC_CHECK_ARG(n_seq > 0 && L > 0 && L <= 32 * ROW_IT && H > 0 && row >= 0 && row < L);
-  LC_CHECK_ARG(ldq >= 3 * H * 64 && ldo >= H * 64 && ldq % 8 == 0 && ldo % 8 == 0 &&
-               ((uintptr_t)O_row & 15) == 0 && (long)L * ldq * 2 < 0x7fffffffL);
-  const int D = H * 64;
-  dim3 grid(n_seq * H);
-  const float scale = 0.125f;
-  const bool online = attn_fwd_online();
-  switch ((L + 31) / 32) {
-#define LC_AFR(Q)                                                                               \
-  case Q:                                                                                      \
-    if (online)                                                                                \
-      hipLaunchKernelGGL((attn_fwd_kernel<Q, true, true>), grid, dim3(64 * Q), 0, st, L, H, D, \
-                         (const bf16_t*)qkv, ldq, (bf16_t*)O_row, ldo, lse_row, causal, scale, \
-                         row);                                                                 \
-    else                                                                                       \
-      hipLaunchKernelGGL((attn_fwd_kernel<Q, false, true>), grid, dim3(64 * Q), 0, st, L, H, D,\
-                         (const bf16_t*)qkv, ldq, (bf16_t*)O_row, ldo, lse_row, causal, scale, \
-                         row);                                                                 \
-    break;
-    LC_AFR(1) LC_AFR(2) LC_AFR(3) LC_AFR(4) LC_AFR(5) LC_AFR(6) LC_AFR(7) LC_AFR(8)
-#undef LC_AFR
-    default:
-      return LC_EINVAL;
-  }
-  LC_LAUNCH_RET();
+  return run(E_ROW_FWD, {st, n_seq, L, H, causal, (const bf16_t*)qkv, ldq, (const bf16_t*)O_row,
+                         ldo, lse_row, nullptr, nullptr, 0, row});
 }
 
 int lc_attn_row_bwd(hipStream_t st, int n_seq, int L, int H, const void* qkv, long ldq, int row,
                     const void* O_row, const void* dO_row, long ldo, const float* lse_row,
                     void* dqkv, long lddq, int causal) {
-  LC_CHECK_ARG(n_seq > 0 && L > 0 && L <= 32 * ROW_IT && H > 0 && row >= 0 && row < L);
-  LC_CHECK_ARG(ldq >= 3 * H * 64 && ldo >= H * 64 && lddq >= 3 * H * 64 && ldq % 8 == 0 &&
-               ldo % 8 == 0 && lddq % 8 == 0 && ((uintptr_t)O_row & 15) == 0 &&
-               ((uintptr_t)dO_row & 15) == 0 && ((uintptr_t)dqkv & 15) == 0 &&
-               (long)L * ldq * 2 < 0x7fffffffL && (long)L * lddq * 2 < 0x7fffffffL);
-  hipLaunchKernelGGL(attn_row_bwd_kernel, dim3(n_seq * H), dim3(ROW_NTH), 0, st, L, H, H * 64,
-                     (const bf16_t*)qkv, ldq, row, (const bf16_t*)O_row, (const bf16_t*)dO_row,
-                     ldo, lse_row, (bf16_t*)dqkv, lddq, causal, 0.125f);
-  LC_LAUNCH_RET();
+  return run(E_ROW_BWD, {st, n_seq, L, H, causal, (const bf16_t*)qkv, ldq, (const bf16_t*)O_row,
+                         ldo, lse_row, (const bf16_t*)dO_row, (bf16_t*)dqkv, lddq, row});
 }
 
 }  // extern "C"
+

@@ -1815,8 +1815,6 @@ tn_reduce_kernel(TnProb p0, TnProb p1) {
   }
 }
 
-int cu_count();
-
 // Walkers per panel so that the problems of one launch fill about one workgroup per CU.
 void plan_tn(TnProb& p, int total_panels) {
   // measured (adapter dW, M = 50 432): one walker per CU 60 us; 2 per CU 80 us (twice the
@@ -1873,19 +1871,6 @@ int launch_nt(const GemmArgs& g) {
 }
 
 int g_split_mode = -1;  // LC_GEMM_SPLITK=0 disables the split-K tail (A/B experiments)
-
-int cu_count() {
-  static int cus[64] = {0};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
-  if (cus[dev] == 0) {
-    int n = 0;
-    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0)
-      n = 256;
-    cus[dev] = n;
-  }
-  return cus[dev];
-}
 
 // Split-K plan for the tail round (see SplitK): S slices of >= min_units k-units each (units =
 // the kernel's k-steps), R*S <= CUs, only when the last round is at most half full and the

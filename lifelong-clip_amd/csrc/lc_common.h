@@ -19,6 +19,21 @@ inline const char* lc_diag_env(const char* name) {
 #endif
 }
 
+// Compute units of the current device, asked once per device; 256 (the MI355X's) when there is
+// no device to ask. The one count every persistent grid and walker plan is sized by.
+inline int cu_count() {
+  static int cus[64] = {0};
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
+  if (cus[dev] == 0) {
+    int n = 0;
+    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0)
+      n = 256;
+    cus[dev] = n;
+  }
+  return cus[dev];
+}
+
 typedef uint16_t bf16_t;  // raw bf16 bits in global memory
 typedef short bf16x8 __attribute__((ext_vector_type(8)));
 typedef short bf16x4 __attribute__((ext_vector_type(4)));

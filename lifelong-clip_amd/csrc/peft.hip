@@ -519,18 +519,6 @@ adapter_bwd_fused_kernel(int M, const bf16_t* __restrict__ G, long ldg,
   }
 }
 
-int ad_cu_count() {
-  static int n = 0;
-  if (n == 0) {
-    int dev = 0, v = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0)
-      v = 256;
-    n = v;
-  }
-  return n;
-}
-
 // ---------------------------------------------------------------------------- AdamW
 __global__ void finite_kernel(long n, const float* __restrict__ g, int* __restrict__ flag) {
   int bad = 0;
@@ -1354,14 +1342,7 @@ static int lora_grad_ws(hipStream_t st, int M, int N, int K, int r, const void* 
   LC_CHECK_ARG(ldy % 8 == 0 && ldx % 8 == 0 && lda % 8 == 0 && ldbt % 8 == 0);
   LC_CHECK_ARG(ldy >= N && ldx >= K && lda >= K && ldbt >= N);
   const int nblk = (M + 31) / 32;
-  int walkers = 0;
-  {
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-      cus = 256;
-    walkers = nblk < cus ? nblk : cus;
-  }
+  const int walkers = nblk < cu_count() ? nblk : cu_count();
   const long slot = (long)N * r + (long)r * K;
   LC_CHECK_ARG(ws_bytes >= LC_SPLITK_TICKET_BYTES + (long)walkers * slot * 4);
   float* part = reinterpret_cast<float*>(static_cast<char*>(ws) + LC_SPLITK_TICKET_BYTES);
@@ -1456,12 +1437,8 @@ static int adapter_ln_fwd(hipStream_t st, int M, int D, const void* z, long ldz,
                ((uintptr_t)resid & 15) == 0);
   LC_CHECK_ARG(ldz >= D && ldx >= D && ldy >= D && keep > 0.f && keep <= 1.f);
   LC_CHECK_ARG(z && Wd && bd && Wu && bu && resid && xout && hout && gamma && beta && y && mean && rstd);
-  int dev = 0, cus = 256;
-  if (hipGetDevice(&dev) != hipSuccess ||
-      hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-    cus = 256;
   const int nblk = (M + 15) / 16;
-  const int grid = nblk < cus ? nblk : cus;
+  const int grid = nblk < cu_count() ? nblk : cu_count();
 #define LC_ALN(DD, XT)                                                                           \
   hipLaunchKernelGGL((adapter_ln_fwd_kernel<DD, XT>), dim3(grid), dim3(512), 0, st, M,           \
                      (const bf16_t*)z, ldz, (const bf16_t*)Wd, bd, (const bf16_t*)Wu, bu, scale,  \
@@ -1542,7 +1519,7 @@ int lc_adapter_bwd_g16(hipStream_t st, int M, int D, const void* gout, long ldg,
                ((uintptr_t)WuT & 15) == 0 && ((uintptr_t)WdT & 15) == 0 &&
                (dz == nullptr || ((uintptr_t)dz & 15) == 0));
   const int nb = (M + AD_R - 1) / AD_R;
-  const dim3 grid(nb < ad_cu_count() ? nb : ad_cu_count()), block(64 * AD_NW);
+  const dim3 grid(nb < cu_count() ? nb : cu_count()), block(64 * AD_NW);
   auto G = static_cast<const bf16_t*>(gout);
   auto H = static_cast<const bf16_t*>(h);
   auto U = static_cast<const bf16_t*>(WuT);
@@ -1576,7 +1553,7 @@ int lc_adapter_bwd(hipStream_t st, int M, int D, const void* gout, long ldg, con
   if (fused && dz != nullptr && (D == 768 || D == 512) && M >= 1024 && ((uintptr_t)gout & 15) == 0 &&
       ((uintptr_t)h & 15) == 0 && ((uintptr_t)WuT & 15) == 0 && ((uintptr_t)WdT & 15) == 0) {
     const int nb = (M + AD_R - 1) / AD_R;
-    const dim3 grid(nb < ad_cu_count() ? nb : ad_cu_count()), block(64 * AD_NW);
+    const dim3 grid(nb < cu_count() ? nb : cu_count()), block(64 * AD_NW);
     auto G = static_cast<const bf16_t*>(gout);
     auto H = static_cast<const bf16_t*>(h);
     auto U = static_cast<const bf16_t*>(WuT);

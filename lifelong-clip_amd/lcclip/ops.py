@@ -372,19 +372,40 @@ def eot_rows(tokens, out):
     return out
 
 
+def _attn_operands(fn, o, qkv, O, dO=None, dqkv=None, same_type=True):
+    """One attention call's 16-bit operands (`o` names O in the messages): O and dO share the one
+    row stride the library is given, and, the library reading raw pointers, all of them share
+    the 16-bit storage type (same_type=False: the fp8 form, bf16 in and codes out)."""
+    if dO is not None and O.stride(0) != dO.stride(0):
+        raise ValueError(f"{o} and d{o} must share a row stride")
+    ts = [t for t in (qkv, O, dO, dqkv) if t is not None]
+    if same_type and (len({t.dtype for t in ts}) != 1 or qkv.dtype not in HALF):
+        names = ("qkv", o) if dO is None else ("qkv", o, f"d{o}", "dqkv")
+        raise TypeError(f"{fn}: {', '.join(names[:-1])} and {names[-1]} must share the 16-bit type")
+
+
+def _attn_row_shapes(fn, qkv, O_row, lse_row, n_seq, L, H, dO_row=None, dqkv=None):
+    """The compact operands of the one-row forms: one O / dO row and H lse values per sequence."""
+    bad = tuple(O_row.shape) != (n_seq, H * 64) or O_row.stride(1) != 1 \
+        or lse_row.numel() != n_seq * H or lse_row.dtype != F32 or not lse_row.is_contiguous() \
+        or qkv.shape[0] != n_seq * L
+    if dO_row is not None:  # the backward forms
+        bad = bad or tuple(dO_row.shape) != (n_seq, H * 64) or dO_row.stride(1) != 1 \
+            or tuple(dqkv.shape) != (n_seq * L, 3 * H * 64)
+    if bad:
+        raise ValueError(f"{fn}: shape mismatch: O_row / dO_row [n_seq, H*64], lse_row f32 "
+                         "[n_seq*H], qkv [n_seq*L, .], dqkv [n_seq*L, 3*H*64]")
+
+
 def attn_fwd(qkv, O, lse, n_seq, L, H, causal):
-    if O.dtype != qkv.dtype or qkv.dtype not in HALF:
-        raise TypeError("attn_fwd: qkv and O must share the 16-bit type")
+    _attn_operands("attn_fwd", "O", qkv, O)
     call(_sym16("lc_attn_fwd", qkv, O), stream_of(qkv), n_seq, L, H, ptr(qkv), qkv.stride(0), ptr(O), O.stride(0),
          ptr(lse), int(causal))
     return O
 
 
 def attn_bwd(qkv, O, dO, lse, dqkv, n_seq, L, H, causal):
-    if O.stride(0) != dO.stride(0):
-        raise ValueError("O and dO must share a row stride")
-    if len({t.dtype for t in (qkv, O, dO, dqkv)}) != 1 or qkv.dtype not in HALF:
-        raise TypeError("attn_bwd: qkv, O, dO and dqkv must share the 16-bit type")
+    _attn_operands("attn_bwd", "O", qkv, O, dO, dqkv)
     call(_sym16("lc_attn_bwd", qkv, O, dO, dqkv), stream_of(qkv), n_seq, L, H, ptr(qkv), qkv.stride(0), ptr(O), ptr(dO),
          O.stride(0), ptr(lse), ptr(dqkv), dqkv.stride(0), int(causal))
     return dqkv
@@ -393,11 +414,8 @@ def attn_bwd(qkv, O, dO, lse, dqkv, n_seq, L, H, causal):
 def attn_row_fwd(qkv, O_row, lse_row, n_seq, L, H, row, causal):
     """Query row `row` of every sequence: O_row [n_seq, H*64] and lse_row [n_seq*H] are that row
     of attn_fwd's O and lse (lc_attn_row_fwd)."""
-    if O_row.dtype != qkv.dtype or qkv.dtype not in HALF:
-        raise TypeError("attn_row_fwd: qkv and O_row must share the 16-bit type")
-    if tuple(O_row.shape) != (n_seq, H * 64) or O_row.stride(1) != 1 or lse_row.numel() != n_seq * H \
-            or lse_row.dtype != F32 or not lse_row.is_contiguous() or qkv.shape[0] != n_seq * L:
-        raise ValueError("attn_row_fwd: O_row [n_seq, H*64], lse_row f32 [n_seq*H], qkv [n_seq*L, .]")
+    _attn_operands("attn_row_fwd", "O_row", qkv, O_row)
+    _attn_row_shapes("attn_row_fwd", qkv, O_row, lse_row, n_seq, L, H)
     call(_sym16("lc_attn_row_fwd", qkv, O_row), stream_of(qkv), n_seq, L, H, ptr(qkv), qkv.stride(0),
          int(row), ptr(O_row), O_row.stride(0), ptr(lse_row), int(causal))
     return O_row
@@ -406,15 +424,8 @@ def attn_row_fwd(qkv, O_row, lse_row, n_seq, L, H, row, causal):
 def attn_row_bwd(qkv, O_row, dO_row, lse_row, dqkv, n_seq, L, H, row, causal):
     """attn_bwd with dO zero off row `row` of every sequence, from the compact O_row / dO_row /
     lse_row: all n_seq*L rows of dqkv are written (lc_attn_row_bwd)."""
-    if O_row.stride(0) != dO_row.stride(0):
-        raise ValueError("O_row and dO_row must share a row stride")
-    if len({t.dtype for t in (qkv, O_row, dO_row, dqkv)}) != 1 or qkv.dtype not in HALF:
-        raise TypeError("attn_row_bwd: qkv, O_row, dO_row and dqkv must share the 16-bit type")
-    if tuple(O_row.shape) != (n_seq, H * 64) or tuple(dO_row.shape) != (n_seq, H * 64) \
-            or O_row.stride(1) != 1 or dO_row.stride(1) != 1 or lse_row.numel() != n_seq * H \
-            or lse_row.dtype != F32 or not lse_row.is_contiguous() \
-            or qkv.shape[0] != n_seq * L or tuple(dqkv.shape) != (n_seq * L, 3 * H * 64):
-        raise ValueError("attn_row_bwd: shape mismatch")
+    _attn_operands("attn_row_bwd", "O_row", qkv, O_row, dO_row, dqkv)
+    _attn_row_shapes("attn_row_bwd", qkv, O_row, lse_row, n_seq, L, H, dO_row, dqkv)
     call(_sym16("lc_attn_row_bwd", qkv, O_row, dO_row, dqkv), stream_of(qkv), n_seq, L, H, ptr(qkv),
          qkv.stride(0), int(row), ptr(O_row), ptr(dO_row), O_row.stride(0), ptr(lse_row), ptr(dqkv),
          dqkv.stride(0), int(causal))
@@ -427,15 +438,8 @@ def attn_bwd_live_row(qkv, O_row, dO_row, lse_row, dqkv, n_seq, L, H, row, causa
     (lc_attn_bwd_live_row: the MFMA backward kernel's single-row mode). Returns False, nothing
     launched, where the library does not cover the case: the caller then blanks and runs
     attn_bwd."""
-    if O_row.stride(0) != dO_row.stride(0):
-        raise ValueError("O_row and dO_row must share a row stride")
-    if len({t.dtype for t in (qkv, O_row, dO_row, dqkv)}) != 1 or qkv.dtype not in HALF:
-        raise TypeError("attn_bwd_live_row: qkv, O_row, dO_row and dqkv must share the 16-bit type")
-    if tuple(O_row.shape) != (n_seq, H * 64) or tuple(dO_row.shape) != (n_seq, H * 64) \
-            or O_row.stride(1) != 1 or dO_row.stride(1) != 1 or lse_row.numel() != n_seq * H \
-            or lse_row.dtype != F32 or not lse_row.is_contiguous() \
-            or qkv.shape[0] != n_seq * L or tuple(dqkv.shape) != (n_seq * L, 3 * H * 64):
-        raise ValueError("attn_bwd_live_row: shape mismatch")
+    _attn_operands("attn_bwd_live_row", "O_row", qkv, O_row, dO_row, dqkv)
+    _attn_row_shapes("attn_bwd_live_row", qkv, O_row, lse_row, n_seq, L, H, dO_row, dqkv)
     name = _sym16("lc_attn_bwd_live_row", qkv, O_row, dO_row, dqkv)
     fn = getattr(load(), name, None)
     if fn is None or fn.argtypes is None:  # an older A/B library
@@ -452,8 +456,7 @@ def attn_bwd_live_row(qkv, O_row, dO_row, lse_row, dqkv, n_seq, L, H, row, causa
 def attn_bwd_fp8(qkv, O, dO, lse, q, n_seq, L, H, causal):
     """attn_bwd with dq|dk|dv written straight into q, an Fp8Mat [n_seq*L, 3*H*64] (the fp8
     QKV input-gradient GEMM's A operand; the codes of attn_bwd + quant_fp8). L <= 224."""
-    if O.stride(0) != dO.stride(0):
-        raise ValueError("O and dO must share a row stride")
+    _attn_operands("attn_bwd_fp8", "O", qkv, O, dO, same_type=False)
     if q.rows != n_seq * L or q.K != 3 * H * 64:
         raise ValueError("attn_bwd_fp8: output shape mismatch")
     call("lc_attn_bwd_fp8", stream_of(qkv), n_seq, L, H, ptr(qkv), qkv.stride(0), ptr(O), ptr(dO),

@@ -1,13 +1,16 @@
-"""Same kernels, same grids: python trace_compare.py OUT_DIR (the traces of trace_ab.sh).
-Per trace: the sequence, in dispatch order, of (kernel name, grid, workgroup size, LDS size) of
-every kernel whose name contains "gemm" or "Cijk_" (hipBLASLt's, and the Tensile GEMMs of the
-tests' torch references), tree against parent, line by line. Exit status 1 on any difference."""
+"""Same kernels, same grids: python trace_compare.py OUT_DIR [SUBSTRING ...] (the traces of a
+trace_ab.sh). Per trace: the sequence, in dispatch order, of (kernel name, grid, workgroup size,
+LDS size) of every kernel whose name contains one of the substrings, as given or in lower case —
+by default "gemm" or "Cijk_" (hipBLASLt's, and the Tensile GEMMs of the tests' torch references);
+profiles/attn_host passes "attn" — tree against parent, line by line. Exit status 1 on any
+difference."""
 import csv
 import glob
 import os
 import sys
 
 out = sys.argv[1]
+keys = sys.argv[2:] or ["gemm", "Cijk_"]
 ok = True
 
 
@@ -18,7 +21,7 @@ def launches(d):
         rows.sort(key=lambda r: int(r["Dispatch_Id"]))
         for r in rows:
             name = r["Kernel_Name"]
-            if "gemm" in name.lower() or "Cijk_" in name:
+            if any(k in name or k in name.lower() for k in keys):
                 seq.append((name,) + tuple(r[c] for c in (
                     "Grid_Size_X", "Grid_Size_Y", "Grid_Size_Z", "Workgroup_Size_X",
                     "Workgroup_Size_Y", "Workgroup_Size_Z", "LDS_Block_Size")))
