@@ -269,6 +269,12 @@ int lc_layernorm_bwd_fp8_x16(hipStream_t stream, int rows, int D, const void* dy
 /* im2col of NCHW f32 images into bf16 patches [n*g*g, 3*P*P] in conv1's (c, kh, kw) order.
  * Replaces: the input side of conv1 (model.py:756-758). */
 int lc_patchify(hipStream_t stream, int n_img, int res, int patch, const float* img, void* out);
+/* lc_patchify for any patch size (res % patch == 0) into rows of stride ldo: out [n*g*g, ldo],
+ * columns 3*P*P .. ldo-1 written as zero, so a K-padded conv1 weight with zero pad columns gives
+ * conv1's sums unchanged (ViT-L/14: 588 -> 640 columns). ldo >= 3*P*P, ldo % 8 == 0, out 16-B
+ * aligned. With patch % 8 == 0 and ldo == 3*P*P the result is lc_patchify's, bit for bit. */
+int lc_patchify_pad(hipStream_t stream, int n_img, int res, int patch, const float* img, void* out,
+                    long ldo);
 
 /* x[n][0] = cls + pos[0]; x[n][1+p] = patch[n*np+p] + pos[1+p]   (model.py:759-764). */
 int lc_vit_assemble(hipStream_t stream, int n_img, int n_patch, int D, const float* patch,
@@ -340,6 +346,23 @@ int lc_attn_bwd_live_row(hipStream_t stream, int n_seq, int L, int H, const void
 int lc_attn_bwd_live_row_f16(hipStream_t stream, int n_seq, int L, int H, const void* qkv,
                              long ldq, int row, const void* O_row, const void* dO_row, long ldo,
                              const float* lse_row, void* dqkv, long lddq, int causal);
+/* lc_attn_fwd / lc_attn_bwd for 257 <= L <= 512 (ViT-L/14 at 224 px: 257 tokens; 262 / 277 with
+ * MVP's prompt rows): the same operands, layouts and rounding points, on a kernel family of its
+ * own — one workgroup of 8 waves per (sequence, head), each wave walking two 32-row chunks, the
+ * whole key / query range in LDS. Every length has one home: L <= 256 is LC_EINVAL here, as
+ * L > 256 is above. ldq, ldo, lddq % 8 == 0 and < 2^21 elements (32-bit byte offsets over up to
+ * 512 padded rows); O and dqkv 16-B aligned. One backward form (key-major, then query-major
+ * kernel): lc_attn_bwd_set_form does not apply. */
+int lc_attn_long_fwd(hipStream_t stream, int n_seq, int L, int H, const void* qkv, long ldq,
+                     void* O, long ldo, float* lse, int causal);
+int lc_attn_long_bwd(hipStream_t stream, int n_seq, int L, int H, const void* qkv, long ldq,
+                     const void* O, const void* dO, long ldo, const float* lse, void* dqkv,
+                     long lddq, int causal);
+int lc_attn_long_fwd_f16(hipStream_t stream, int n_seq, int L, int H, const void* qkv, long ldq,
+                         void* O, long ldo, float* lse, int causal);
+int lc_attn_long_bwd_f16(hipStream_t stream, int n_seq, int L, int H, const void* qkv, long ldq,
+                         const void* O, const void* dO, long ldo, const float* lse, void* dqkv,
+                         long lddq, int causal);
 /* The backward with dq|dk|dv written as the A operand of the fp8 QKV input-gradient GEMM
  * (lc_gemm_nt_fp8): e4m3 codes dqkv [n_seq*L, lddq BYTES] (lddq % 16 == 0, 16-B aligned) + E8M0
  * scales q_scale [3*H*64/128][q_rows][4] (q_rows = n_seq*L rounded up to 256), bit-identical to
@@ -668,6 +691,8 @@ int lc_adapter_wgrad_ws_f16(hipStream_t stream, int M, int D, const void* gout, 
 /* The image tower at the reference's own arithmetic (AdapterCLIP(image_precision="fp16"):
  * conv1's im2col rows and the first ln_1 output in IEEE half, the residual stream f32). */
 int lc_patchify_f16(hipStream_t stream, int n_img, int res, int patch, const float* img, void* out);
+int lc_patchify_pad_f16(hipStream_t stream, int n_img, int res, int patch, const float* img,
+                        void* out, long ldo);
 int lc_vit_embed_ln_f16(hipStream_t stream, int n_img, int n_patch, int D, const float* patch,
                         const float* cls, const float* pos, const float* ln_pre_w,
                         const float* ln_pre_b, float* x0, const float* ln1_w, const float* ln1_b,

@@ -1466,10 +1466,453 @@ attn_row_bwd_kernel(int L, int H, int D, const bf16_t* __restrict__ qkv, long ld
   }
 }
 
+// ------------------------------------------------------------- long family, 257 <= L <= 512 keys
+// NCH = ceil(L / 32) = 9..16 chunks, LP = 32 * NCH padded rows. One workgroup of 8 waves per
+// (sequence, head) with the whole key (backward, key-major: query) range in LDS; wave w walks the
+// 32-row chunks w and w + 8 one after the other. Each chunk's body is that of the one-wave-per-
+// chunk kernels above — attn_fwd_kernel's online pass, attn_bwd_kv_kernel's query sweep,
+// attn_bwd_q_kernel's key sweep, the same rounding points — so a wave's register demand is that
+// of their 8-chunk instances. LDS: forward K + V images LP * 288 B (82 944 .. 147 456), key-major
+// Q + dO + -lse + -D LP * 264 B (<= 135 168), query-major K + V LP * 256 B (<= 131 072): one
+// workgroup per CU, which is what bounds residency (no minimum-occupancy argument).
+// Staging is ceil(LP * 8 / 512) passes of 512 16-B pieces, rows guarded against LP (an odd NCH
+// leaves the last pass half full); the swizzle's 16-row period keeps the lane offsets valid.
+constexpr int LONG_NTH = 512, LONG_WAVES = 8;
+
+template <int NCH>
+__global__ void __launch_bounds__(LONG_NTH)
+attn_long_fwd_kernel(int L, int H, int D, const bf16_t* __restrict__ qkv, long ldq,
+                     bf16_t* __restrict__ O, long ldo, float* __restrict__ lse, int causal,
+                     float scale) {
+  constexpr int LP = 32 * NCH;
+  __shared__ __attribute__((aligned(16))) char smem[LP * 128 + LP * V_STRIDE];
+  char* Ks = smem;
+  char* Vs = smem + LP * 128;
+
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int g = lane >> 4, t = lane & 15;
+  const int nh = blockIdx.x, n = nh / H, h = nh % H;
+  const long base = (long)n * L;
+  const float c = scale * LOG2E;
+
+  // staging through the sequence's descriptor: rows >= L read zero, rows >= LP are not written
+  constexpr int IT = (LP * 8 + LONG_NTH - 1) / LONG_NTH;
+  const int ch = tid & 7;
+  const auto rq = seq_rsrc(qkv, base, ldq * 2, L);
+  uint4 kv[IT], vv[IT];
+#pragma unroll
+  for (int i = 0; i < IT; ++i) {
+    const int r = (tid + i * LONG_NTH) >> 3;
+    const int off = r * (int)ldq * 2 + (h * 64 + ch * 8) * 2;  // (r <= 511: check())
+    kv[i] = seq_ld16(rq, off + D * 2);
+    vv[i] = seq_ld16(rq, off + D * 4);
+  }
+#pragma unroll
+  for (int i = 0; i < IT; ++i) {
+    const int r = (tid + i * LONG_NTH) >> 3;
+    if (r < LP) {
+      *reinterpret_cast<uint4*>(Ks + r * 128 + swz(r, ch) * 16) = kv[i];
+      *reinterpret_cast<uint4*>(Vs + r * V_STRIDE + ch * 16) = vv[i];
+    }
+  }
+  __syncthreads();
+
+  const char* k0 = Ks + row_off(t, g, 0);
+  const char* k1 = Ks + row_off(t, g, 1);
+  const char* vt = Vs + (4 * g + (t >> 2)) * V_STRIDE + (t & 3) * 8;
+
+#pragma unroll 1
+  for (int qc = w; qc < NCH; qc += LONG_WAVES) {  // (no barrier below)
+    const int qb = 32 * qc;
+    bf16x8 qf[2][2];
+#pragma unroll
+    for (int qt = 0; qt < 2; ++qt) {
+      const int q = qb + qt * 16 + t;
+#pragma unroll
+      for (int s = 0; s < 2; ++s) {
+        uint4 u = seq_ld16(rq, q * (int)ldq * 2 + (h * 64 + s * 32 + g * 8) * 2);
+        qf[qt][s] = *reinterpret_cast<bf16x8*>(&u);
+      }
+    }
+    // key steps holding a key <= the chunk's last query (causal) / < L
+    const int s_end = causal ? min(NCH, qc + 1) : NCH;
+
+    float sm[2] = {0.f, 0.f}, nm[2] = {0.f, 0.f};
+    f32x4 Oa[4][2];
+#pragma unroll
+    for (int dt = 0; dt < 4; ++dt) Oa[dt][0] = Oa[dt][1] = f32x4{0.f, 0.f, 0.f, 0.f};
+    float mr[2] = {-INFINITY, -INFINITY};  // running raw-score max per query
+#pragma unroll 1
+    for (int s = 0; s < s_end; ++s) {
+      // S^T tile pair: lane holds S^T[key = 32s + 16kk + 4g + r][q = qb + 16qt + t]
+      f32x4 S[2][2];
+#pragma unroll
+      for (int kk = 0; kk < 2; ++kk) {
+        const int ro = (32 * s + 16 * kk) * 128;
+        const bf16x8 ka = lds16(k0 + ro), kb = lds16(k1 + ro);
+#pragma unroll
+        for (int qt = 0; qt < 2; ++qt) {
+          S[kk][qt] = mfma16(ka, qf[qt][0], f32x4{0.f, 0.f, 0.f, 0.f});
+          S[kk][qt] = mfma16(kb, qf[qt][1], S[kk][qt]);
+        }
+      }
+      if (32 * s + 32 > L || (causal && 32 * s + 31 > qb)) {  // wave-uniform edge block
+#pragma unroll
+        for (int kk = 0; kk < 2; ++kk)
+#pragma unroll
+          for (int qt = 0; qt < 2; ++qt)
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+              S[kk][qt][r] = masked(32 * s + 16 * kk + 4 * g + r, qb + 16 * qt + t, L, causal)
+                                 ? -INFINITY : S[kk][qt][r];
+      }
+#pragma unroll
+      for (int qt = 0; qt < 2; ++qt) {
+        float m = fmaxf(fmaxf(fmaxf(S[0][qt][0], S[0][qt][1]), fmaxf(S[0][qt][2], S[0][qt][3])),
+                        fmaxf(fmaxf(S[1][qt][0], S[1][qt][1]), fmaxf(S[1][qt][2], S[1][qt][3])));
+        m = fmaxf(m, __shfl_xor(m, 16));
+        m = fmaxf(m, __shfl_xor(m, 32));
+        const float mn = fmaxf(mr[qt], m);  // finite from block 0 on (key 0 is never masked)
+        const float corr = ex2((mr[qt] - mn) * c);
+        mr[qt] = mn;
+        nm[qt] = -mn * c;
+        sm[qt] *= corr;
+#pragma unroll
+        for (int dt = 0; dt < 4; ++dt) Oa[dt][qt] *= corr;
+      }
+#pragma unroll
+      for (int kk = 0; kk < 2; ++kk)
+#pragma unroll
+        for (int qt = 0; qt < 2; ++qt)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const float p = ex2(__builtin_fmaf(S[kk][qt][r], c, nm[qt]));
+            S[kk][qt][r] = p;
+            sm[qt] += p;
+          }
+      const bf16x8 pb0 = pack8(S[0][0], S[1][0]);
+      const bf16x8 pb1 = pack8(S[0][1], S[1][1]);
+      const char* vs = vt + 32 * s * V_STRIDE;
+#pragma unroll
+      for (int dt = 0; dt < 4; ++dt) {
+        const bf16x8 vf = cat4(lds_tr(vs + dt * 32), lds_tr(vs + 16 * V_STRIDE + dt * 32));
+        Oa[dt][0] = mfma16(vf, pb0, Oa[dt][0]);
+        Oa[dt][1] = mfma16(vf, pb1, Oa[dt][1]);
+      }
+    }
+    // lane holds O^T[d = dt*16 + 4g + r][q = qb + qt*16 + t]
+#pragma unroll
+    for (int qt = 0; qt < 2; ++qt) {
+      float l = sm[qt];
+      l += __shfl_xor(l, 16);
+      l += __shfl_xor(l, 32);
+      const int q = qb + qt * 16 + t;
+      if (q < L) {
+        const float inv = 1.0f / l;
+        uint2 x[4];
+#pragma unroll
+        for (int dt = 0; dt < 4; ++dt) {
+          const f32x4 o = Oa[dt][qt];
+          x[dt] = uint2{pack2bf(o[0] * inv, o[1] * inv), pack2bf(o[2] * inv, o[3] * inv)};
+        }
+        store_row64(O + (base + q) * ldo + h * 64, g, x);
+        if (g == 0) lse[(long)nh * L + q] = mr[qt] * c + __log2f(l);
+      }
+    }
+  }
+}
+
+// key-major (dK, dV): Q, dO, -lse, -D of every query in LDS; a wave's key chunks in turn
+template <int NCH>
+__global__ void __launch_bounds__(LONG_NTH)
+attn_long_bwd_kv_kernel(int L, int H, int D, const bf16_t* __restrict__ qkv, long ldq,
+                        const bf16_t* __restrict__ O, const bf16_t* __restrict__ dO, long ldo,
+                        const float* __restrict__ lse, bf16_t* __restrict__ dqkv, long lddq,
+                        int causal, float scale) {
+  constexpr int LP = 32 * NCH;
+  __shared__ __attribute__((aligned(16))) char smem[2 * LP * 128 + 2 * LP * 4];
+  char* Qs = smem;
+  char* dOs = smem + LP * 128;
+  float* nlse_s = reinterpret_cast<float*>(smem + 2 * LP * 128);  // -lse
+  float* nd_s = nlse_s + LP;                                       // -D
+
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int g = lane >> 4, t = lane & 15;
+  const int nh = blockIdx.x, n = nh / H, h = nh % H;
+  const long base = (long)n * L;
+  const float c = scale * LOG2E;
+
+  // staging, one pass of 512 16-B pieces at a time (three row images' registers per pass);
+  // D = rowsum(dO*O) from the same chunks (8 lanes per row, reduced with xor-shuffles)
+  constexpr int IT = (LP * 8 + LONG_NTH - 1) / LONG_NTH;
+  const int ch = tid & 7;
+#pragma unroll 2
+  for (int i = 0; i < IT; ++i) {
+    const int r = (tid + i * LONG_NTH) >> 3;
+    const long off = h * 64 + ch * 8;
+    const uint4 qv = ld16_or_zero(qkv + (base + r) * ldq + off, r < L);
+    const uint4 dv = ld16_or_zero(dO + (base + r) * ldo + off, r < L);
+    const uint4 ov = ld16_or_zero(O + (base + r) * ldo + off, r < L);
+    const float lv = (r < L) ? lse[(long)nh * L + r] : 1e30f;
+    const uint32_t aa[4] = {ov.x, ov.y, ov.z, ov.w};
+    const uint32_t bb[4] = {dv.x, dv.y, dv.z, dv.w};
+    float dsum = 0.f;
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+      dsum += bf2f(aa[k] & 0xffff) * bf2f(bb[k] & 0xffff) + bf2f(aa[k] >> 16) * bf2f(bb[k] >> 16);
+    dsum = sum_row8(dsum);  // (every lane of the wave takes part: r is guarded below)
+    if (r < LP) {
+      *reinterpret_cast<uint4*>(Qs + r * 128 + swz(r, ch) * 16) = qv;
+      *reinterpret_cast<uint4*>(dOs + r * 128 + swz(r, ch) * 16) = dv;
+      if (ch == 0) {
+        nd_s[r] = -dsum;
+        nlse_s[r] = r < L ? -lv : -1e30f;
+      }
+    }
+  }
+  __syncthreads();
+
+  const int ro0 = row_off(t, g, 0), ro1 = row_off(t, g, 1);
+  const int tro[4] = {tr_off(t, g, 0), tr_off(t, g, 1), tr_off(t, g, 2), tr_off(t, g, 3)};
+
+#pragma unroll 1
+  for (int kc = w; kc < NCH; kc += LONG_WAVES) {  // (no barrier below)
+    // own key block: K / V rows kb + kt2*16 + t, as B-operand fragments
+    const int kb = 32 * kc;
+    bf16x8 kf[2][2], vf[2][2];
+#pragma unroll
+    for (int kt2 = 0; kt2 < 2; ++kt2) {
+      const int key = kb + kt2 * 16 + t;
+#pragma unroll
+      for (int s = 0; s < 2; ++s) {
+        const bf16_t* src = qkv + (base + key) * ldq + h * 64 + s * 32 + g * 8;
+        uint4 ku = ld16_or_zero(src + D, key < L), vu = ld16_or_zero(src + 2 * D, key < L);
+        kf[kt2][s] = *reinterpret_cast<bf16x8*>(&ku);
+        vf[kt2][s] = *reinterpret_cast<bf16x8*>(&vu);
+      }
+    }
+    f32x4 dV[4][2], dK[4][2];
+#pragma unroll
+    for (int dt = 0; dt < 4; ++dt)
+#pragma unroll
+      for (int k2 = 0; k2 < 2; ++k2) dV[dt][k2] = dK[dt][k2] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+    // causal: queries before the block's first key see none of its keys
+    const int qc0 = causal ? kc : 0;
+#pragma unroll 1
+    for (int qc = qc0; qc < NCH; ++qc) {
+      const bool edge = (kb + 32 > L) || (causal && kb + 31 > qc * 32);
+      // B operands (k = 32 queries of this chunk): slot j<4 -> q = 4g+j, j>=4 -> 16+4g+(j-4);
+      // one 16-query tile of S / dP is live at a time and packed to bf16 straight away.
+      u32x4 pw[2], sw[2];
+#pragma unroll
+      for (int qt = 0; qt < 2; ++qt) {
+        const int q0 = qc * 32 + qt * 16 + 4 * g;
+        const f32x4 nl = *reinterpret_cast<const f32x4*>(nlse_s + q0);
+        const f32x4 nd = *reinterpret_cast<const f32x4*>(nd_s + q0);
+        const char* qrow = Qs + (qc * 32 + qt * 16) * 128;
+        const char* drow = dOs + (qc * 32 + qt * 16) * 128;
+        const bf16x8 qa0 = lds16(qrow + ro0), qa1 = lds16(qrow + ro1);
+        const bf16x8 da0 = lds16(drow + ro0), da1 = lds16(drow + ro1);
+        f32x4 S[2], dP[2];
+#pragma unroll
+        for (int k2 = 0; k2 < 2; ++k2) {
+          S[k2] = mfma16(qa0, kf[k2][0], f32x4{0.f, 0.f, 0.f, 0.f});
+          S[k2] = mfma16(qa1, kf[k2][1], S[k2]);
+          dP[k2] = mfma16(da0, vf[k2][0], nd);  // dP - D
+          dP[k2] = mfma16(da1, vf[k2][1], dP[k2]);
+        }
+        // lane holds X[q = q0 + r][key = kb + k2*16 + t]
+#pragma unroll
+        for (int k2 = 0; k2 < 2; ++k2) {
+          f32x4 p;
+#pragma unroll
+          for (int r = 0; r < 4; ++r) p[r] = ex2(__builtin_fmaf(S[k2][r], c, nl[r]));
+          if (edge) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+              p[r] = masked(kb + k2 * 16 + t, q0 + r, L, causal) ? 0.f : p[r];
+          }
+          const f32x4 ds = p * dP[k2];
+          pw[k2][2 * qt] = pack2bf(p[0], p[1]);
+          pw[k2][2 * qt + 1] = pack2bf(p[2], p[3]);
+          sw[k2][2 * qt] = pack2bf(ds[0], ds[1]);
+          sw[k2][2 * qt + 1] = pack2bf(ds[2], ds[3]);
+        }
+      }
+      const bf16x8 pB[2] = {as_bf8(pw[0]), as_bf8(pw[1])};
+      const bf16x8 sB[2] = {as_bf8(sw[0]), as_bf8(sw[1])};
+      const char* qblk = Qs + qc * 32 * 128;
+      const char* dblk = dOs + qc * 32 * 128;
+#pragma unroll
+      for (int dt = 0; dt < 4; ++dt) {
+        const bf16x8 doT = cat4(lds_tr(dblk + tro[dt]), lds_tr(dblk + 16 * 128 + tro[dt]));
+        const bf16x8 qT = cat4(lds_tr(qblk + tro[dt]), lds_tr(qblk + 16 * 128 + tro[dt]));
+#pragma unroll
+        for (int k2 = 0; k2 < 2; ++k2) {
+          dV[dt][k2] = mfma16(doT, pB[k2], dV[dt][k2]);
+          dK[dt][k2] = mfma16(qT, sB[k2], dK[dt][k2]);
+        }
+      }
+    }
+    // dK, dV of the key block: lane holds X^T[d = dt*16 + 4g + r][key = kb + k2*16 + t]
+#pragma unroll
+    for (int k2 = 0; k2 < 2; ++k2) {
+      const int key = kb + k2 * 16 + t;
+      if (key < L) {
+        bf16_t* dst = dqkv + (base + key) * lddq + h * 64;
+#pragma unroll
+        for (int dt = 0; dt < 4; ++dt) {
+          const f32x4 a = dK[dt][k2], b = dV[dt][k2];
+          *reinterpret_cast<uint2*>(dst + D + dt * 16 + 4 * g) =
+              uint2{pack2bf(a[0] * scale, a[1] * scale), pack2bf(a[2] * scale, a[3] * scale)};
+          *reinterpret_cast<uint2*>(dst + 2 * D + dt * 16 + 4 * g) =
+              uint2{pack2bf(b[0], b[1]), pack2bf(b[2], b[3])};
+        }
+      }
+    }
+  }
+}
+
+// query-major (dQ): K and V of every key in LDS; a wave's query chunks in turn
+template <int NCH>
+__global__ void __launch_bounds__(LONG_NTH)
+attn_long_bwd_q_kernel(int L, int H, int D, const bf16_t* __restrict__ qkv, long ldq,
+                       const bf16_t* __restrict__ O, const bf16_t* __restrict__ dO, long ldo,
+                       const float* __restrict__ lse, bf16_t* __restrict__ dqkv, long lddq,
+                       int causal, float scale) {
+  constexpr int LP = 32 * NCH;
+  __shared__ __attribute__((aligned(16))) char smem[2 * LP * 128];
+  char* Ks = smem;
+  char* Vs = smem + LP * 128;
+
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int g = lane >> 4, t = lane & 15;
+  // reverse order: the key-major kernel touched the last heads most recently (L2 / Infinity Cache)
+  const int nh = gridDim.x - 1 - blockIdx.x, n = nh / H, h = nh % H;
+  const long base = (long)n * L;
+  const float c = scale * LOG2E;
+
+  constexpr int IT = (LP * 8 + LONG_NTH - 1) / LONG_NTH;
+  const int ch = tid & 7;
+  uint4 kv[IT], vv[IT];
+#pragma unroll
+  for (int i = 0; i < IT; ++i) {
+    const int r = (tid + i * LONG_NTH) >> 3;
+    const bf16_t* src = qkv + (base + r) * ldq + h * 64 + ch * 8;
+    kv[i] = ld16_or_zero(src + D, r < L);
+    vv[i] = ld16_or_zero(src + 2 * D, r < L);
+  }
+#pragma unroll
+  for (int i = 0; i < IT; ++i) {
+    const int r = (tid + i * LONG_NTH) >> 3;
+    if (r < LP) {
+      *reinterpret_cast<uint4*>(Ks + r * 128 + swz(r, ch) * 16) = kv[i];
+      *reinterpret_cast<uint4*>(Vs + r * 128 + swz(r, ch) * 16) = vv[i];
+    }
+  }
+  __syncthreads();
+
+  const int ro0 = row_off(t, g, 0), ro1 = row_off(t, g, 1);
+  const int tro[4] = {tr_off(t, g, 0), tr_off(t, g, 1), tr_off(t, g, 2), tr_off(t, g, 3)};
+
+#pragma unroll 1
+  for (int qc = w; qc < NCH; qc += LONG_WAVES) {  // (no barrier below)
+    const int qb = 32 * qc;
+    bf16x8 qf[2][2], df[2][2];
+    float nl[2], nd[2];
+#pragma unroll
+    for (int qt = 0; qt < 2; ++qt) {
+      const int q = qb + qt * 16 + t;
+      float dsum = 0.f;
+#pragma unroll
+      for (int s = 0; s < 2; ++s) {
+        const long off = h * 64 + s * 32 + g * 8;
+        uint4 u = ld16_or_zero(qkv + (base + q) * ldq + off, q < L);
+        uint4 d = ld16_or_zero(dO + (base + q) * ldo + off, q < L);
+        uint4 o = ld16_or_zero(O + (base + q) * ldo + off, q < L);
+        qf[qt][s] = *reinterpret_cast<bf16x8*>(&u);
+        df[qt][s] = *reinterpret_cast<bf16x8*>(&d);
+        const uint32_t oo[4] = {o.x, o.y, o.z, o.w}, dd[4] = {d.x, d.y, d.z, d.w};
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+          dsum += bf2f(oo[k] & 0xffff) * bf2f(dd[k] & 0xffff) + bf2f(oo[k] >> 16) * bf2f(dd[k] >> 16);
+      }
+      dsum += __shfl_xor(dsum, 16);
+      dsum += __shfl_xor(dsum, 32);
+      nd[qt] = -dsum;
+      nl[qt] = q < L ? -lse[(long)nh * L + q] : -1e30f;
+    }
+    const int s_end = causal ? min(NCH, qc + 1) : NCH;
+
+    f32x4 dQ[4][2];
+#pragma unroll
+    for (int dt = 0; dt < 4; ++dt) dQ[dt][0] = dQ[dt][1] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll 1
+    for (int s = 0; s < s_end; ++s) {
+      const bool edge = (32 * s + 32 > L) || (causal && 32 * s + 31 > qb);
+      // one 16-key tile of S^T / dP^T live at a time, packed to bf16 straight away
+      u32x4 sw[2];
+#pragma unroll
+      for (int kk = 0; kk < 2; ++kk) {
+        const int ro = (32 * s + 16 * kk) * 128;
+        const bf16x8 ka0 = lds16(Ks + ro + ro0), ka1 = lds16(Ks + ro + ro1);
+        const bf16x8 va0 = lds16(Vs + ro + ro0), va1 = lds16(Vs + ro + ro1);
+        f32x4 S[2], dP[2];
+#pragma unroll
+        for (int qt = 0; qt < 2; ++qt) {
+          S[qt] = mfma16(ka0, qf[qt][0], f32x4{0.f, 0.f, 0.f, 0.f});
+          S[qt] = mfma16(ka1, qf[qt][1], S[qt]);
+          dP[qt] = mfma16(va0, df[qt][0], f32x4{nd[qt], nd[qt], nd[qt], nd[qt]});
+          dP[qt] = mfma16(va1, df[qt][1], dP[qt]);
+        }
+        // lane holds X^T[key = 32s + 16kk + 4g + r][q = qb + qt*16 + t]
+#pragma unroll
+        for (int qt = 0; qt < 2; ++qt) {
+          f32x4 p;
+#pragma unroll
+          for (int r = 0; r < 4; ++r) p[r] = ex2(__builtin_fmaf(S[qt][r], c, nl[qt]));
+          if (edge) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+              p[r] = masked(32 * s + 16 * kk + 4 * g + r, qb + qt * 16 + t, L, causal) ? 0.f : p[r];
+          }
+          const f32x4 ds = p * dP[qt];
+          sw[qt][2 * kk] = pack2bf(ds[0], ds[1]);
+          sw[qt][2 * kk + 1] = pack2bf(ds[2], ds[3]);
+        }
+      }
+      const bf16x8 sb0 = as_bf8(sw[0]);
+      const bf16x8 sb1 = as_bf8(sw[1]);
+      const char* kblk = Ks + 32 * s * 128;
+#pragma unroll
+      for (int dt = 0; dt < 4; ++dt) {
+        const bf16x8 kT = cat4(lds_tr(kblk + tro[dt]), lds_tr(kblk + 16 * 128 + tro[dt]));
+        dQ[dt][0] = mfma16(kT, sb0, dQ[dt][0]);
+        dQ[dt][1] = mfma16(kT, sb1, dQ[dt][1]);
+      }
+    }
+    // lane holds dQ^T[d = dt*16 + 4g + r][q = qb + qt*16 + t]
+#pragma unroll
+    for (int qt = 0; qt < 2; ++qt) {
+      const int q = qb + qt * 16 + t;
+      if (q < L) {
+        bf16_t* dst = dqkv + (base + q) * lddq + h * 64;
+#pragma unroll
+        for (int dt = 0; dt < 4; ++dt) {
+          const f32x4 a = dQ[dt][qt];
+          *reinterpret_cast<uint2*>(dst + dt * 16 + 4 * g) =
+              uint2{pack2bf(a[0] * scale, a[1] * scale), pack2bf(a[2] * scale, a[3] * scale)};
+        }
+      }
+    }
+  }
+}
+
 // --------------------------------------------------------------------------------- host side
 // One attention launch (include/lc_clip.h has the operands' contract). The extern "C" entry
 // points fill it, casts done there; check(), route() and the family launchers read it.
-enum Entry { E_FWD, E_ROW_FWD, E_BWD, E_FP8, E_LIVE_ROW, E_ROW_BWD };
+enum Entry { E_FWD, E_ROW_FWD, E_BWD, E_FP8, E_LIVE_ROW, E_ROW_BWD, E_LONG_FWD, E_LONG_BWD };
 struct AttnArgs {
   hipStream_t stream;
   int n_seq, L, H, causal;
@@ -1494,6 +1937,8 @@ constexpr float ATTN_SCALE = 0.125f;  // 64^-0.5
 // modes and the two-phase kernel, which hold every chunk in LDS (BwdLds<8> does not fit, so
 // attn_bwd_kernel<8> without ROW must not be instantiated)
 constexpr int MAX_CHUNKS = 8, FUSED_MAX_CHUNKS = 7;
+// the long family's: 257 <= L <= 512, so that every length has one home
+constexpr int LONG_MIN_CHUNKS = MAX_CHUNKS + 1, LONG_MAX_CHUNKS = 16;
 
 // 32-bit offsets. The kernels reach a sequence's rows through a raw-buffer descriptor and an int
 // byte offset r * (int)ld * 2 + column bytes. r runs over the PADDED rows, up to 32 * NQB - 1
@@ -1505,14 +1950,21 @@ constexpr int MAX_CHUNKS = 8, FUSED_MAX_CHUNKS = 7;
 // then (ld < 2^22 elements; the fp8 form's lddq, in bytes, < 2^23), the same in all six launches.
 constexpr long MAX_ROW_BYTES = 1L << 23;
 static_assert(32 * MAX_CHUNKS * (MAX_ROW_BYTES - 16) < OOR && ROW_IT <= MAX_CHUNKS, "see above");
+// The long family's padded rows run to 32 * LONG_MAX_CHUNKS - 1 = 511: half the stride then
+// (ld < 2^21 elements), 512 * (2^22 - 16) = 2^31 - 8192.
+constexpr long LONG_MAX_ROW_BYTES = 1L << 22;
+static_assert(32 * LONG_MAX_CHUNKS * (LONG_MAX_ROW_BYTES - 16) < OOR, "see above");
 bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 // The one argument check: which fields entry point e has, and which limits apply to it.
 int check(const AttnArgs& a, Entry e) {
-  const bool fwd = e == E_FWD || e == E_ROW_FWD, fp8 = e == E_FP8;
+  const bool lng = e == E_LONG_FWD || e == E_LONG_BWD;
+  const bool fwd = e == E_FWD || e == E_ROW_FWD || e == E_LONG_FWD, fp8 = e == E_FP8;
   const bool row_pair = e == E_ROW_FWD || e == E_ROW_BWD, one_row = row_pair || e == E_LIVE_ROW;
-  const int max_L = 32 * (fp8 ? FUSED_MAX_CHUNKS : row_pair ? ROW_IT : MAX_CHUNKS);
-  LC_CHECK_ARG(a.n_seq > 0 && a.L > 0 && a.L <= max_L && a.H > 0);
+  const int max_L = 32 * (lng ? LONG_MAX_CHUNKS : fp8 ? FUSED_MAX_CHUNKS : row_pair ? ROW_IT
+                                                                          : MAX_CHUNKS);
+  const int min_L = lng ? 32 * MAX_CHUNKS + 1 : 1;
+  LC_CHECK_ARG(a.n_seq > 0 && a.L >= min_L && a.L <= max_L && a.H > 0);
   LC_CHECK_ARG(one_row == (a.row >= 0) && a.row < a.L);
   const long D = a.D(), es = fp8 ? 1 : 2;  // es: bytes per dqkv element
   LC_CHECK_ARG(a.ldq >= 3 * D && a.ldq % 8 == 0 && a.ldo >= D && a.ldo % 8 == 0);
@@ -1525,8 +1977,8 @@ int check(const AttnArgs& a, Entry e) {
   if (fp8)
     LC_CHECK_ARG(a.q_scale != nullptr && a.q_rows % 256 == 0 &&
                  a.q_rows >= ((long)a.n_seq * a.L + 255) / 256 * 256);
-  LC_CHECK_ARG(a.ldq < MAX_ROW_BYTES / 2 && a.ldo < MAX_ROW_BYTES / 2 &&
-               a.lddq < MAX_ROW_BYTES / es);
+  const long max_rb = lng ? LONG_MAX_ROW_BYTES : MAX_ROW_BYTES;
+  LC_CHECK_ARG(a.ldq < max_rb / 2 && a.ldo < max_rb / 2 && a.lddq < max_rb / es);
   return LC_OK;
 }
 
@@ -1548,11 +2000,13 @@ const bool g_fwd_online = [] {  // DIAG builds: LCCLIP_ATTN_FWD_ONLINE=0: the tw
 }();
 
 // The kernel family a checked launch runs on, decided here and nowhere else (table: DESIGN.md).
-enum Family { F_REFUSE, F_FORWARD, F_FUSED, F_SPLIT, F_TWO_PHASE, F_ROW_VALU };
+enum Family { F_REFUSE, F_FORWARD, F_FUSED, F_SPLIT, F_TWO_PHASE, F_ROW_VALU, F_LONG };
 Family route(Entry e, int nqb, int form) {
   switch (e) {
     case E_FWD: case E_ROW_FWD: return F_FORWARD;
     case E_ROW_BWD: return F_ROW_VALU;
+    // 9..16 chunks: one form, whatever lc_attn_bwd_set_form says
+    case E_LONG_FWD: case E_LONG_BWD: return F_LONG;
     case E_FP8: return F_FUSED;
     // the result is the default form's (fused kernel; key-major + query-major pair at 8 chunks)
     case E_LIVE_ROW: return form == 0 || form == ATTN_BWD_FUSED ? F_FUSED : F_REFUSE;
@@ -1564,12 +2018,12 @@ Family route(Entry e, int nqb, int form) {
   return form == ATTN_BWD_TWO_PHASE ? F_TWO_PHASE : F_FUSED;
 }
 
-// f(std::integral_constant<int, nqb>) for nqb in 1..MAX (the family's chunk limit: nothing
-// beyond it is instantiated), LC_EINVAL outside; f(std::true_type / std::false_type) for a flag
-template <int MAX, class F>
+// f(std::integral_constant<int, nqb>) for nqb in MIN..MAX (the family's chunk limits: nothing
+// outside them is instantiated), LC_EINVAL outside; f(std::true_type / std::false_type) for a flag
+template <int MAX, int MIN = 1, class F>
 int with_chunks(int nqb, const F& f) {
-  if constexpr (MAX == 0) return LC_EINVAL;
-  else return nqb == MAX ? f(std::integral_constant<int, MAX>{}) : with_chunks<MAX - 1>(nqb, f);
+  if constexpr (MAX < MIN) return LC_EINVAL;
+  else return nqb == MAX ? f(std::integral_constant<int, MAX>{}) : with_chunks<MAX - 1, MIN>(nqb, f);
 }
 template <class F>
 int with_flag(bool flag, const F& f) {
@@ -1650,6 +2104,27 @@ int launch_row_valu(const AttnArgs& a) {
   LC_LAUNCH_RET();
 }
 
+// the long family: the forward, or the key-major (dK, dV) then the query-major (dQ) kernel
+int launch_long(Entry e, const AttnArgs& a) {
+  return with_chunks<LONG_MAX_CHUNKS, LONG_MIN_CHUNKS>(a.nqb(), [&](auto Q) -> int {
+    constexpr int NCH = decltype(Q)::value;
+    if (e == E_LONG_FWD) {
+      hipLaunchKernelGGL(attn_long_fwd_kernel<NCH>, dim3(a.items()), dim3(LONG_NTH), 0, a.stream,
+                         a.L, a.H, a.D(), a.qkv, a.ldq, const_cast<bf16_t*>(a.O), a.ldo,
+                         const_cast<float*>(a.lse), a.causal, ATTN_SCALE);
+      LC_LAUNCH_RET();
+    }
+    auto launch = [&](auto kern) {
+      hipLaunchKernelGGL(kern, dim3(a.items()), dim3(LONG_NTH), 0, a.stream, a.L, a.H, a.D(),
+                         a.qkv, a.ldq, a.O, a.dO, a.ldo, a.lse, a.dqkv, a.lddq, a.causal,
+                         ATTN_SCALE);
+    };
+    launch(attn_long_bwd_kv_kernel<NCH>);
+    launch(attn_long_bwd_q_kernel<NCH>);
+    LC_LAUNCH_RET();
+  });
+}
+
 // Every launching entry point: check, route, launch on the family the route names.
 int run(Entry e, const AttnArgs& a) {
   if (const int rc = check(a, e)) return rc;
@@ -1661,6 +2136,7 @@ int run(Entry e, const AttnArgs& a) {
     case F_SPLIT: return launch_split(a);
     case F_TWO_PHASE: return launch_two_phase(a);
     case F_ROW_VALU: return launch_row_valu(a);
+    case F_LONG: return launch_long(e, a);
     case F_REFUSE: break;
   }
   return LC_EUNSUPPORTED;
@@ -1693,6 +2169,19 @@ int lc_attn_bwd(hipStream_t st, int n_seq, int L, int H, const void* qkv, long l
                 const void* dO, long ldo, const float* lse, void* dqkv, long lddq, int causal) {
   return run(E_BWD, {st, n_seq, L, H, causal, (const bf16_t*)qkv, ldq, (const bf16_t*)O, ldo, lse,
                      (const bf16_t*)dO, (bf16_t*)dqkv, lddq});
+}
+
+int lc_attn_long_fwd(hipStream_t st, int n_seq, int L, int H, const void* qkv, long ldq, void* O,
+                     long ldo, float* lse, int causal) {
+  return run(E_LONG_FWD, {st, n_seq, L, H, causal, (const bf16_t*)qkv, ldq, (const bf16_t*)O, ldo,
+                          lse});
+}
+
+int lc_attn_long_bwd(hipStream_t st, int n_seq, int L, int H, const void* qkv, long ldq,
+                     const void* O, const void* dO, long ldo, const float* lse, void* dqkv,
+                     long lddq, int causal) {
+  return run(E_LONG_BWD, {st, n_seq, L, H, causal, (const bf16_t*)qkv, ldq, (const bf16_t*)O, ldo,
+                          lse, (const bf16_t*)dO, (bf16_t*)dqkv, lddq});
 }
 
 int lc_attn_bwd_live_row(hipStream_t st, int n_seq, int L, int H, const void* qkv, long ldq,

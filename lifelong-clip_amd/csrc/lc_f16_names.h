@@ -10,6 +10,8 @@
 #define lc_attn_row_fwd lc_attn_row_fwd_f16
 #define lc_attn_row_bwd lc_attn_row_bwd_f16
 #define lc_attn_bwd_live_row lc_attn_bwd_live_row_f16
+#define lc_attn_long_fwd lc_attn_long_fwd_f16
+#define lc_attn_long_bwd lc_attn_long_bwd_f16
 #define lc_gemm_nt_ex lc_gemm_nt_ex_f16
 #define lc_gemm_nt lc_gemm_nt_f16
 #define lc_gemm_nt_ws lc_gemm_nt_ws_f16
@@ -28,6 +30,7 @@
 #define lc_layernorm_bwd lc_layernorm_bwd_f16
 #define lc_layernorm_bwd_fp8 lc_layernorm_bwd_fp8_f16
 #define lc_patchify lc_patchify_f16
+#define lc_patchify_pad lc_patchify_pad_f16
 #define lc_vit_assemble lc_vit_assemble_f16
 #define lc_vit_embed_ln lc_vit_embed_ln_f16
 #define lc_text_embed lc_text_embed_f16

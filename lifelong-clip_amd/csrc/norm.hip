@@ -262,6 +262,32 @@ __global__ void patchify_kernel(int n_img, int res, int P, const float* __restri
   }
 }
 
+// patchify_kernel for any P into rows of stride ldo (ldo % 8 == 0): 8 columns per thread, read
+// one by one (a patch-14 row starts at no 16-B boundary), columns >= 3*P*P written as zero
+__global__ void patchify_pad_kernel(int n_img, int res, int P, const float* __restrict__ img,
+                                    bf16_t* __restrict__ out, long ldo) {
+  const int g = res / P;
+  const int cols = 3 * P * P;
+  const long c8 = ldo / 8;
+  const long total8 = (long)n_img * g * g * c8;
+  for (long e = blockIdx.x * (long)blockDim.x + threadIdx.x; e < total8;
+       e += (long)gridDim.x * blockDim.x) {
+    const long row = e / c8;
+    const int col0 = (int)(e % c8) * 8;
+    const int n = (int)(row / (g * g)), pp = (int)(row % (g * g));
+    const int py = pp / g, px = pp % g;
+    float v[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const int col = col0 + j;
+      const int c = col / (P * P), rem = col % (P * P), ky = rem / P, kx = rem % P;
+      v[j] = col < cols ? img[(((long)n * 3 + c) * res + (py * P + ky)) * res + px * P + kx] : 0.f;
+    }
+    *reinterpret_cast<uint4*>(out + row * ldo + col0) =
+        uint4{pack2bf(v[0], v[1]), pack2bf(v[2], v[3]), pack2bf(v[4], v[5]), pack2bf(v[6], v[7])};
+  }
+}
+
 // x[n][0] = cls + pos[0]; x[n][1+p] = patch[n*np + p] + pos[1+p]   (model.py:759-764)
 __global__ void vit_assemble_kernel(int n_img, int np, int D, const float* __restrict__ patch,
                                     const float* __restrict__ cls, const float* __restrict__ pos,
@@ -537,6 +563,17 @@ int lc_patchify(hipStream_t st, int n_img, int res, int patch, const float* img,
   const long work = (long)n_img * res * res * 3 / 8;
   hipLaunchKernelGGL(patchify_kernel, dim3(grid_for(work, 256)), dim3(256), 0, st, n_img, res,
                      patch, img, (bf16_t*)out);
+  LC_LAUNCH_RET();
+}
+
+int lc_patchify_pad(hipStream_t st, int n_img, int res, int patch, const float* img, void* out,
+                    long ldo) {
+  LC_CHECK_ARG(n_img > 0 && patch > 0 && res > 0 && res % patch == 0);
+  LC_CHECK_ARG(ldo >= 3L * patch * patch && ldo % 8 == 0 && ((uintptr_t)out & 15) == 0);
+  const int g = res / patch;
+  const long work = (long)n_img * g * g * (ldo / 8);
+  hipLaunchKernelGGL(patchify_pad_kernel, dim3(grid_for(work, 256)), dim3(256), 0, st, n_img, res,
+                     patch, img, (bf16_t*)out, ldo);
   LC_LAUNCH_RET();
 }
 

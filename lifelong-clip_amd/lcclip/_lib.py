@@ -43,12 +43,15 @@ SIGNATURES = {
     "lc_layernorm_bwd_fp8": [P, c_int, c_int, P, c_int, c_long, P, c_long, P, P, P, P, P, P, c_long,
                              P, P, c_long, P, c_long],
     "lc_patchify": [P, c_int, c_int, c_int, P, P],
+    "lc_patchify_pad": [P, c_int, c_int, c_int, P, P, c_long],
     "lc_vit_assemble": [P, c_int, c_int, c_int, P, P, P, P],
     "lc_vit_embed_ln": [P, c_int, c_int, c_int, P, P, P, P, P, P, P, P, P, P, P],
     "lc_text_embed": [P, c_int, c_int, c_int, P, P, P, P],
     "lc_eot_rows": [P, c_int, c_int, P, P],
     "lc_attn_fwd": [P, c_int, c_int, c_int, P, c_long, P, c_long, P, c_int],
     "lc_attn_bwd": [P, c_int, c_int, c_int, P, c_long, P, P, c_long, P, P, c_long, c_int],
+    "lc_attn_long_fwd": [P, c_int, c_int, c_int, P, c_long, P, c_long, P, c_int],
+    "lc_attn_long_bwd": [P, c_int, c_int, c_int, P, c_long, P, P, c_long, P, P, c_long, c_int],
     "lc_attn_row_fwd": [P, c_int, c_int, c_int, P, c_long, c_int, P, c_long, P, c_int],
     "lc_attn_row_bwd": [P, c_int, c_int, c_int, P, c_long, c_int, P, P, c_long, P, P, c_long, c_int],
     "lc_attn_bwd_live_row": [P, c_int, c_int, c_int, P, c_long, c_int, P, P, c_long, P, P, c_long,
@@ -114,12 +117,12 @@ F16_ENTRY_POINTS = ("lc_gemm_nt", "lc_gemm_nt_ws", "lc_gemm_nt_rows", "lc_gemm_t
                     "lc_gemm_set_tile", "lc_gemm_set_streamk",
                     "lc_layernorm_fwd", "lc_layernorm_bwd", "lc_attn_fwd", "lc_attn_bwd",
                     "lc_attn_bwd_set_form", "lc_attn_row_fwd", "lc_attn_row_bwd",
-                    "lc_attn_bwd_live_row",
+                    "lc_attn_bwd_live_row", "lc_attn_long_fwd", "lc_attn_long_bwd",
                     "lc_adapter_fwd_rows", "lc_adapter_ln_fwd_rows",
                     "lc_cast_bf16", "lc_merge_weight", "lc_cast_weights_bf16",
                     "lc_merge_weights_bf16", "lc_lora_grad", "lc_lora_grad_ws", "lc_adapter_fwd",
                     "lc_adapter_ln_fwd", "lc_adapter_bwd", "lc_adapter_wgrad",
-                    "lc_adapter_wgrad_ws", "lc_patchify", "lc_vit_embed_ln")
+                    "lc_adapter_wgrad_ws", "lc_patchify", "lc_patchify_pad", "lc_vit_embed_ln")
 SIGNATURES.update({n + "_f16": SIGNATURES[n] for n in F16_ENTRY_POINTS})
 # the image tower's half residual stream (include/lc_clip.h "x16"): the f32 forms' arguments
 SIGNATURES.update({n + "_x16": SIGNATURES[n] for n in (

@@ -22,7 +22,13 @@ ARCHITECTURES = {
     "ViT-B/32": dict(embed_dim=512, image_resolution=224, vision_layers=12, vision_width=768,
                      vision_patch_size=32, context_length=77, vocab_size=49408,
                      transformer_width=512, transformer_heads=8, transformer_layers=12),
+    # the reference adapter script's model (scripts/adapter_clip.sh:30): 257 image tokens
+    "ViT-L/14": dict(embed_dim=768, image_resolution=224, vision_layers=24, vision_width=1024,
+                     vision_patch_size=14, context_length=77, vocab_size=49408,
+                     transformer_width=768, transformer_heads=12, transformer_layers=12),
 }
+# the spelling the reference's scripts pass (MODEL_NAME="ViT-L-14") for the same entries
+ALIASES = {name.replace("/", "-"): name for name in ARCHITECTURES}
 
 
 def available_models():
@@ -33,6 +39,7 @@ def load(name: str, device=None, jit: bool = False, design_details=None, arch_ov
     design_details = dict(design_details or {})
     if jit:
         raise ValueError("TorchScript CLIP archives are not supported; pass jit=False")
+    name = ALIASES.get(name, name) if not os.path.isfile(name) else name
     if os.path.isfile(name):
         sd = torch.load(name, map_location="cpu", weights_only=True)
         if "state_dict" in sd:

@@ -568,6 +568,9 @@ class BlockStack:
                              "prompt rows, or the frozen (prompt) tower")
         if last_rows and not (self.rows_ok() and not prompts and not replace and stop is None):
             raise ValueError("last_rows: the bf16 adapter stack without prompt rows")
+        if last_rows and L > ops.ATTN_ROW_MAX_L:
+            raise ValueError(f"last_rows: the one-row attention forms take L <= "
+                             f"{ops.ATTN_ROW_MAX_L} (got {L})")
         c.last_ln = last_ln if (last_ln is not None
                                 and self.last_ln_fused(D, prompts, stop)) else None
         ln1 = first_ln1 if plan and plan[0].plain else None
@@ -1165,8 +1168,16 @@ class ImageTower:
         if key != self._key:
             W = v.conv1.weight.shape[0]
             dev = v.conv1.weight.device
-            self.conv_w = _empty((W, v.conv1.weight[0].numel()), dt, dev)
-            ops.merge_weight(v.conv1.weight.detach().reshape(W, -1), None, None, 0.0, self.conv_w)
+            K = v.conv1.weight[0].numel()
+            # conv1's GEMM takes K % 64 == 0: a patch size that gives another K (14: 588) runs
+            # at Kp = 640 on zero pad columns, which add exact zeros to every sum
+            self.conv_k = Kp = -(-K // 64) * 64
+            if Kp == K:
+                self.conv_w = _empty((W, K), dt, dev)
+                ops.merge_weight(v.conv1.weight.detach().reshape(W, -1), None, None, 0.0, self.conv_w)
+            else:
+                self.conv_w = torch.zeros((W, Kp), dtype=dt, device=dev)
+                self.conv_w[:, :K].copy_(v.conv1.weight.detach().reshape(W, -1))
             E = v.proj.shape[1]
             self.projT = _empty((E, W), dt, dev)      # forward: f = x @ proj  -> B = proj^T
             self.proj = _empty((W, E), dt, dev)       # backward: dx = df @ proj^T -> B = proj
@@ -1194,9 +1205,13 @@ class ImageTower:
         P = v.patch_size
         g = v.input_resolution // P
         npch = g * g
+        Kp = self.conv_k
         if img.dim() == 2:
             # conv1's bf16 im2col rows, already produced by the fused train transform
             # (lcclip.transforms.TrainTransform(..., layout="patches"))
+            if Kp != 3 * P * P:
+                raise ValueError(f"patch-row input needs 3 * patch^2 % 64 == 0 (patch {P}): pass "
+                                 "NCHW images")
             if img.dtype != BF16 or img.shape[1] != 3 * P * P or img.shape[0] % npch:
                 raise ValueError(f"patch input must be bf16 [n*{npch}, {3 * P * P}]")
             n = img.shape[0] // npch
@@ -1205,8 +1220,11 @@ class ImageTower:
         else:
             n = img.shape[0]
             img = img.contiguous().to(F32)
-            patches = _empty((n * npch, 3 * P * P), self.stack.dt, dev)
-            ops.patchify(img, P, patches)
+            patches = _empty((n * npch, Kp), self.stack.dt, dev)
+            if Kp == 3 * P * P:
+                ops.patchify(img, P, patches)
+            else:
+                ops.patchify_pad(img, P, patches)
         pe = _empty((n * npch, v.width), F32, dev)
         ops.gemm_nt(patches, self.conv_w, EPI_F32, pe)
         return pe, n, npch
@@ -1334,7 +1352,9 @@ class ImageTower:
         """forward() from a precomputed embed() (the MVP query and prompt passes share x0)."""
         self._stage()
         last = None
-        rows = self.LAST_ROWS and self.stack.rows_ok() and not prompts and not replace
+        # (the compact last block needs the one-row attention forms: up to 256 tokens)
+        rows = (self.LAST_ROWS and self.stack.rows_ok() and not prompts and not replace
+                and L <= ops.ATTN_ROW_MAX_L)
         if x0.dtype == F16 and self.stack.variant == "adapter":
             # ln_post fused into the last block's adapter over every row (rows: the CLS rows)
             v = self.visual

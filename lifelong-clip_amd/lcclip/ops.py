@@ -327,6 +327,24 @@ def patchify(img, patch, out):
     return out
 
 
+def patchify_pad(img, patch, out):
+    """patchify for any patch size into out [n*patches, ldo >= 3*p*p] (ldo % 8 == 0), columns
+    3*p*p .. ldo-1 written as zero (lc_patchify_pad): conv1's im2col rows at a padded K."""
+    if img.dtype != F32 or not img.is_contiguous():
+        raise ValueError("patchify_pad expects a contiguous f32 NCHW batch")
+    n, c, h, w = img.shape
+    if c != 3 or h != w or patch <= 0 or h % patch:
+        raise ValueError("patchify_pad expects square 3-channel images of a whole number of patches")
+    g = h // patch
+    if out.dtype not in HALF or out.dim() != 2 or out.shape[0] != n * g * g \
+            or out.shape[1] < 3 * patch * patch or out.stride(1) != 1 or out.stride(0) != out.shape[1]:
+        raise ValueError("patchify_pad: out must be bf16 / float16 [n*patches, >= 3*p*p], its row "
+                         "stride its width")
+    call(_sym16("lc_patchify_pad", out), stream_of(img), n, h, patch, ptr(img), ptr(out),
+         out.stride(0))
+    return out
+
+
 def vit_assemble(patch_emb, cls, pos, x, n_img, n_patch):
     call("lc_vit_assemble", stream_of(x), n_img, n_patch, x.shape[1], ptr(patch_emb), ptr(cls),
          ptr(pos), ptr(x))
@@ -397,17 +415,31 @@ def _attn_row_shapes(fn, qkv, O_row, lse_row, n_seq, L, H, dO_row=None, dqkv=Non
                          "[n_seq*H], qkv [n_seq*L, .], dqkv [n_seq*L, 3*H*64]")
 
 
+# Every length has one home in the library: lc_attn_fwd / lc_attn_bwd up to ATTN_ROW_MAX_L tokens
+# (as the one-row, live-row and fp8 forms), the long family's entry points up to ATTN_MAX_L.
+ATTN_ROW_MAX_L, ATTN_MAX_L = 256, 512
+
+
+def _attn_symbol(which, L):
+    """lc_attn_fwd / lc_attn_bwd (which: "fwd" / "bwd"), or the long family's at 257..512 tokens."""
+    if L > ATTN_MAX_L:
+        raise ValueError(f"attn_{which}: L = {L} is over the attention kernels' limit of "
+                         f"{ATTN_MAX_L} tokens")
+    return f"lc_attn_{which}" if L <= ATTN_ROW_MAX_L else f"lc_attn_long_{which}"
+
+
 def attn_fwd(qkv, O, lse, n_seq, L, H, causal):
     _attn_operands("attn_fwd", "O", qkv, O)
-    call(_sym16("lc_attn_fwd", qkv, O), stream_of(qkv), n_seq, L, H, ptr(qkv), qkv.stride(0), ptr(O), O.stride(0),
-         ptr(lse), int(causal))
+    call(_sym16(_attn_symbol("fwd", L), qkv, O), stream_of(qkv), n_seq, L, H, ptr(qkv),
+         qkv.stride(0), ptr(O), O.stride(0), ptr(lse), int(causal))
     return O
 
 
 def attn_bwd(qkv, O, dO, lse, dqkv, n_seq, L, H, causal):
     _attn_operands("attn_bwd", "O", qkv, O, dO, dqkv)
-    call(_sym16("lc_attn_bwd", qkv, O, dO, dqkv), stream_of(qkv), n_seq, L, H, ptr(qkv), qkv.stride(0), ptr(O), ptr(dO),
-         O.stride(0), ptr(lse), ptr(dqkv), dqkv.stride(0), int(causal))
+    call(_sym16(_attn_symbol("bwd", L), qkv, O, dO, dqkv), stream_of(qkv), n_seq, L, H, ptr(qkv),
+         qkv.stride(0), ptr(O), ptr(dO), O.stride(0), ptr(lse), ptr(dqkv), dqkv.stride(0),
+         int(causal))
     return dqkv
 
 

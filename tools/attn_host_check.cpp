@@ -6,7 +6,7 @@
 //     -o build/attn_host_check && build/attn_host_check > codes.txt
 //   (the IEEE-half build: add -DLC_F16 -include lc_f16_names.h, which renames the calls below too)
 //
-// One call per argument check of the seven attention entry points, each with an argument that
+// One call per argument check of the nine attention entry points, each with an argument that
 // check rejects, printed as "line code". Every call returns at a check, before any launch; the
 // program fails if one returns another code than expected. Built on two revisions of
 // attention.hip, the outputs show which rejections moved.
@@ -35,6 +35,7 @@ int main() {
   float* f = reinterpret_cast<float*>(buf);
   // 2 sequences of 64 tokens, 2 heads: D = 128, qkv / dqkv rows of 384, O rows of 128
   const long big22 = 1L << 22, big23 = 1L << 23;  // the stride bound, in elements / in bytes
+  const long big21 = 1L << 21;                    // the long family's (512 padded rows)
 
   // lc_attn_fwd(stream, n_seq, L, H, qkv, ldq, O, ldo, lse, causal)
   REJECT(lc_attn_fwd(0, 0, 64, 2, p, 384, p, 128, f, 0));
@@ -121,6 +122,40 @@ int main() {
   REJECT(fn(0, 2, 256, 2, p, 384, 0, p, p, 128, f, p, big22, 0)); /* bound */
   ROW_BWD_CHECKS(lc_attn_row_bwd)
   ROW_BWD_CHECKS(lc_attn_bwd_live_row)
+
+  // lc_attn_long_fwd / lc_attn_long_bwd: lc_attn_fwd / lc_attn_bwd's arguments, 257 <= L <= 512
+  // (2 sequences of 257 tokens), every stride below 2^21 elements
+  REJECT(lc_attn_long_fwd(0, 0, 257, 2, p, 384, p, 128, f, 0));
+  REJECT(lc_attn_long_fwd(0, 2, 256, 2, p, 384, p, 128, f, 0));  // lc_attn_fwd's length
+  REJECT(lc_attn_long_fwd(0, 2, 513, 2, p, 384, p, 128, f, 0));
+  REJECT(lc_attn_long_fwd(0, 2, 257, 0, p, 384, p, 128, f, 0));
+  REJECT(lc_attn_long_fwd(0, 2, 257, 2, p, 376, p, 128, f, 0));
+  REJECT(lc_attn_long_fwd(0, 2, 257, 2, p, 388, p, 128, f, 0));
+  REJECT(lc_attn_long_fwd(0, 2, 257, 2, p, 384, p, 120, f, 0));
+  REJECT(lc_attn_long_fwd(0, 2, 257, 2, p, 384, p, 132, f, 0));
+  REJECT(lc_attn_long_fwd(0, 2, 257, 2, p, 384, odd, 128, f, 0));
+  REJECT(lc_attn_long_fwd(0, 2, 512, 2, p, big21, p, 128, f, 0));  // the bound, at 512 rows
+  REJECT(lc_attn_long_fwd(0, 2, 257, 2, p, 384, p, big21, f, 0));
+  REJECT(lc_attn_long_bwd(0, 0, 257, 2, p, 384, p, p, 128, f, p, 384, 0));
+  REJECT(lc_attn_long_bwd(0, 2, 256, 2, p, 384, p, p, 128, f, p, 384, 0));
+  REJECT(lc_attn_long_bwd(0, 2, 513, 2, p, 384, p, p, 128, f, p, 384, 0));
+  REJECT(lc_attn_long_bwd(0, 2, 257, 0, p, 384, p, p, 128, f, p, 384, 0));
+  REJECT(lc_attn_long_bwd(0, 2, 257, 2, p, 376, p, p, 128, f, p, 384, 0));
+  REJECT(lc_attn_long_bwd(0, 2, 257, 2, p, 388, p, p, 128, f, p, 384, 0));
+  REJECT(lc_attn_long_bwd(0, 2, 257, 2, p, 384, p, p, 120, f, p, 384, 0));
+  REJECT(lc_attn_long_bwd(0, 2, 257, 2, p, 384, p, p, 132, f, p, 384, 0));
+  REJECT(lc_attn_long_bwd(0, 2, 257, 2, p, 384, p, p, 128, f, p, 376, 0));
+  REJECT(lc_attn_long_bwd(0, 2, 257, 2, p, 384, p, p, 128, f, p, 388, 0));
+  REJECT(lc_attn_long_bwd(0, 2, 257, 2, p, 384, p, p, 128, f, odd, 384, 0));
+  REJECT(lc_attn_long_bwd(0, 2, 512, 2, p, big21, p, p, 128, f, p, 384, 0));  // the bound
+  REJECT(lc_attn_long_bwd(0, 2, 257, 2, p, 384, p, p, big21, f, p, 384, 0));
+  REJECT(lc_attn_long_bwd(0, 2, 512, 2, p, 384, p, p, 128, f, p, big21, 0));
+  // (lc_attn_bwd_set_form does not reach the long family: the same rejection under every form)
+  for (int form = 1; form <= 3; ++form) {
+    ACCEPT(lc_attn_bwd_set_form(form));
+    REJECT(lc_attn_long_bwd(0, 2, 256, 2, p, 384, p, p, 128, f, p, 384, 0));
+  }
+  ACCEPT(lc_attn_bwd_set_form(0));
 
   // lc_attn_bwd_set_form: 0..3; lc_attn_bwd_live_row refuses under forms 2 and 3 (valid
   // arguments: it returns before any launch), after its argument checks
