@@ -595,8 +595,13 @@ int lc_softmax_bwd_rows(hipStream_t stream, int B, int C, const float* probs, co
                         float* dlogits);
 
 /* x [n] f32 *= s, s = 2^(target_exp - floor(log2 max|x|)) computed on the device and written to
- * scale[0] (1 when max|x| is 0 or not finite): the loss scaling of the IEEE-half text tower's
- * backward, per call (torch.cuda.amp.GradScaler's role, methods/adapter_clip.py:93). */
+ * scale[0]: the loss scaling of the IEEE-half text tower's backward, per call
+ * (torch.cuda.amp.GradScaler's role, methods/adapter_clip.py:93). The exponent of s is clamped to
+ * [-126, 127]; floor(log2) is the true one for a subnormal maximum too. s = 1 when max|x| is 0 or
+ * infinite. NaN elements are left out of the maximum: s is then the finite power of two of the
+ * other elements, every finite element is scaled exactly, and the NaNs stay NaN in x (so
+ * lc_check_finite still skips the update); s = 1 when every element is NaN.
+ * n > 0, -100 <= target_exp <= 100. */
 int lc_grad_pow2_normalize(hipStream_t stream, long n, float* x, float* scale, int target_exp);
 
 /* y[i] += x[i] / scale[0] (n elements, f32): the scaled gradients back to their true size. */

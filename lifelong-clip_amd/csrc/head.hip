@@ -257,8 +257,10 @@ softmax_bwd_kernel(int B, int C, const float* __restrict__ p, const float* __res
 // (methods/adapter_clip.py:93, _trainer.py:163) — here per call and by a power of two computed
 // on the device from the gradient itself: s = 2^(target - floor(log2 max|x|)), which puts
 // max|x| in [2^target, 2^(target+1)) (the tower's own stores stay within ~1.4x of its input's
-// max, measured: target 10 leaves a 30x margin below half's 65504). A zero or non-finite
-// max gives s = 1. Powers of two make scaling and unscaling exact.
+// max, measured: target 10 leaves a 30x margin below half's 65504). The exponent of s is
+// clamped to [-126, 127]. A zero or infinite max gives s = 1; NaN elements do not take part in
+// the max (fmaxf drops them) and stay NaN in x, so lc_check_finite still sees them. Powers of
+// two make scaling and unscaling exact.
 __global__ void __launch_bounds__(1024)
 grad_pow2_normalize_kernel(long n, float* __restrict__ x, float* __restrict__ s_out, int target) {
   __shared__ float red[16];
@@ -284,7 +286,9 @@ grad_pow2_normalize_kernel(long n, float* __restrict__ x, float* __restrict__ s_
     for (int w = 0; w < 16; ++w) a = fmaxf(a, red[w]);
     float s = 1.0f;
     if (a > 0.f && a <= 3.4e38f) {  // finite, nonzero
-      const int e = (int)((__float_as_uint(a) >> 23) & 0xff) - 127;  // floor(log2 a), normals
+      // floor(log2 a): the exponent field, or for a subnormal a = j 2^-149 the top bit of j
+      const uint32_t bits = __float_as_uint(a);
+      const int e = bits >= 0x00800000u ? (int)(bits >> 23) - 127 : -118 - __clz((int)bits);
       const int k = min(max(target - e, -126), 127);
       s = __uint_as_float((uint32_t)(k + 127) << 23);
     }

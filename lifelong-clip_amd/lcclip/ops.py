@@ -769,7 +769,8 @@ def head_feat_grad(dlogits, sr, sc, other_n, self_n, norms, logit_scale, dF, dn_
 
 def grad_pow2_normalize(x, scale, target_exp=10):
     """x (contiguous f32) *= s in place, s = 2^(target_exp - floor(log2 max|x|)) on the device,
-    written to scale (f32 [1]): the IEEE-half text tower's per-call loss scaling."""
+    written to scale (f32 [1]): the IEEE-half text tower's per-call loss scaling. s = 1 for a zero
+    or infinite maximum; NaN elements are left out of the maximum and stay NaN in x."""
     if x.dtype != F32 or not x.is_contiguous() or scale.dtype != F32 or scale.numel() < 1:
         raise ValueError("grad_pow2_normalize: contiguous f32 x and an f32 scale slot")
     call("lc_grad_pow2_normalize", stream_of(x), x.numel(), ptr(x), ptr(scale), int(target_exp))
