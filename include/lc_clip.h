@@ -387,6 +387,19 @@ int lc_train_transform(hipStream_t stream, int n, int C, int Hin, int Win, const
                        int pad, int crop_i, int crop_j, int flip, const float* mean_host,
                        const float* std_host, int quantize, int layout, int patch, void* out);
 
+/* lc_train_transform's patch rows for any even patch size at a padded row stride: out bf16
+ * [n*(R/patch)^2, ldo], column (c*patch + ky)*patch + kx = pixel (c, py*patch + ky, px*patch + kx)
+ * of the transformed image (the lc_patchify_pad order), columns C*patch^2 .. ldo-1 written as
+ * zero by the same launch (every byte of out is written exactly once; no memset needed).
+ * patch even, R % patch == 0, R % 4 == 0, ldo >= C*patch^2, ldo % 8 == 0, out 16-B aligned;
+ * the other arguments as lc_train_transform. The rows equal lc_train_transform(layout 0)
+ * followed by lc_patchify_pad bit for bit; with patch 16 and ldo == C*256 they are
+ * lc_train_transform(layout 1)'s. ViT-L/14: patch 14, ldo 640 (588 data columns). */
+int lc_train_transform_rows(hipStream_t stream, int n, int C, int Hin, int Win, const float* x,
+                            int R, int pad, int crop_i, int crop_j, int flip,
+                            const float* mean_host, const float* std_host, int quantize, int patch,
+                            int ldo, void* out);
+
 /* AutoAugment (torchvision 0.16 AutoAugment, the 'autoaug' branch of methods/_trainer.py:215-229)
  * on the uint8-quantised batch: x f32 [n, C, H, W] in [0, 1] -> out f32 = augmented uint8 / 255.
  * n_ops (0..2) ops of one drawn sub-policy, shared by the batch (torchvision draws once per call):

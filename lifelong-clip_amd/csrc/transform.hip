@@ -318,6 +318,275 @@ int lc_train_transform(hipStream_t st, int n, int C, int Hin, int Win, const flo
 }  // extern "C"
 
 // ---------------------------------------------------------------------------------------------
+// conv1's patch rows for any even patch size at a padded row stride (lc_train_transform_rows;
+// ViT-L/14: P = 14, C P^2 = 588 columns in rows of ldo = 640). Same f32 operations in the same
+// order as the kernels above, so the rows equal lc_train_transform(layout 0) + lc_patchify_pad
+// bit for bit. A (c, ky) run is P bf16 and starts on a 4-B boundary only (P even), so the unit of
+// work is one 16-B piece of the padded row, assembled from four column pairs: a pair never
+// straddles two runs, a piece may straddle two runs, two channels or the data / pad boundary.
+// The pad columns are written as zero by the same stores: every byte of out exactly once.
+namespace {
+
+LC_DEV float sel4(const float (&a)[4], int c) {  // a[c] without a runtime-indexed array
+  return c == 0 ? a[0] : (c == 1 ? a[1] : (c == 2 ? a[2] : a[3]));
+}
+
+// The four column pairs of piece `piece` (columns 8 piece .. 8 piece + 7) of a patch row:
+// channel (-1: pad columns), ky and kx of each pair's first column.
+struct PiecePairs {
+  int c[4], ky[4], kx[4];
+};
+LC_DEV PiecePairs piece_pairs(int piece, int C, int P) {
+  const int PP = P * P, col = piece * 8;
+  int c = col / PP;
+  const int rem = col - c * PP;
+  int ky = rem / P, kx = rem - ky * P;
+  PiecePairs pp;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    pp.c[k] = c < C ? c : -1;
+    pp.ky[k] = ky;
+    pp.kx[k] = kx;
+    kx += 2;
+    if (kx >= P) {
+      kx = 0;
+      if (++ky >= P) {
+        ky = 0;
+        ++c;
+      }
+    }
+  }
+  return pp;
+}
+
+// Separable form (train_transform_sep_kernel's split) for all C channels of one image and a band
+// of its patch rows. A band of `nrows` output rows blends only the source rows [smin, smax]
+// its first and last in-image rows tap (lin_src is monotone in the output row), at most S of
+// them (the host's bound): workgroup (img, band) stages those rows of every channel quantised,
+// their horizontal pass Hs[c][i - smin][x] and the band's row taps and the column taps in LDS
+// (CIFAR -> 224, one patch row per band: 5 source rows, 2 + 13 + 4 KB), so several workgroups
+// share a CU and one's staging runs under another's stores. Output: lanes own FIXED pieces of
+// the padded row (their column decode is done once) and walk the band's patches, which are
+// consecutive rows of out, so a group of ldo / 8 lanes stores one whole row and the workgroup a
+// run of consecutive rows.
+__global__ void __launch_bounds__(256)
+train_transform_rows_sep_kernel(int C, int Hin, int Win, const float* __restrict__ x, int R,
+                                int pad, int crop_i, int crop_j, int flip, TfParams tp,
+                                int quantize, int P, int ldo, int S, int ob,
+                                bf16_t* __restrict__ out) {
+  extern __shared__ float rows_lds[];
+  const int img = blockIdx.x, tid = threadIdx.x, nthr = blockDim.x;
+  float* simg = rows_lds;                                  // [C][S][Win]
+  float* hs = rows_lds + ((C * S * Win + 3) & ~3);         // [C][S][R]
+  Tap* rows = reinterpret_cast<Tap*>(hs + C * S * R);      // [ob]: the band's output rows
+  Tap* cols = rows + ob;                                   // [R]
+  const int g = R / P;
+  const int p_lo = (int)((long)blockIdx.y * g / gridDim.y);
+  const int p_hi = (int)((long)(blockIdx.y + 1) * g / gridDim.y);  // patch rows [p_lo, p_hi)
+  const int y_lo = p_lo * P, nrows = (p_hi - p_lo) * P;            // nrows <= ob
+  const float sh = (float)Hin / (float)R, sw = (float)Win / (float)R;
+  // the band's first and last rows inside the resized image, and the source rows they span
+  const int pf = max(y_lo + crop_i - pad, 0), pl = min(y_lo + nrows - 1 + crop_i - pad, R - 1);
+  int smin = 0, nsrc = 0;
+  if (pf <= pl) {
+    int a0, a1, b0, b1;
+    float l;
+    lin_src(pf, sh, Hin, a0, a1, l);
+    lin_src(pl, sh, Hin, b0, b1, l);
+    smin = a0;
+    nsrc = min(b1 - a0 + 1, S);
+  }
+  for (int k = tid; k < nrows + R; k += nthr) {
+    const bool is_row = k < nrows;
+    const int o = is_row ? k : k - nrows;
+    // row: RandomCrop offset only; column: hflip of the cropped window, then the offset
+    const int p = is_row ? y_lo + o + crop_i - pad : (flip ? R - 1 - o : o) + crop_j - pad;
+    Tap t{0, 0, 0.f, 0};
+    if (p >= 0 && p < R) {
+      lin_src(p, is_row ? sh : sw, is_row ? Hin : Win, t.i0, t.i1, t.l1);
+      t.ok = 1;
+    }
+    (is_row ? rows : cols)[o] = t;
+  }
+  const float* src = x + (long)img * C * Hin * Win;
+  for (int k = tid; k < C * nsrc * Win; k += nthr) {
+    const int c = k / (nsrc * Win), rem = k - c * nsrc * Win;
+    const int sl = rem / Win, xw = rem - sl * Win;
+    simg[(c * S + sl) * Win + xw] = quant(src[((long)c * Hin + smin + sl) * Win + xw], quantize);
+  }
+  __syncthreads();
+  // horizontal pass: one wave per (channel, source row), lanes over the R output columns
+  for (int ci = tid >> 6; ci < C * nsrc; ci += nthr >> 6) {
+    const int c = ci / nsrc, sl = ci - c * nsrc;
+    const float* r = simg + (c * S + sl) * Win;
+    float* h = hs + (c * S + sl) * R;
+    for (int xo = tid & 63; xo < R; xo += 64) {
+      const Tap t = cols[xo];
+      h[xo] = t.ok ? lerp1(r[t.i0], r[t.i1], t.l1) : 0.f;
+    }
+  }
+  __syncthreads();
+  const int c8 = ldo >> 3;
+  const int gw = c8 < nthr ? c8 : nthr, ngrp = nthr / gw;  // lanes per patch row, rows in flight
+  const int grp = tid / gw, lp = tid - grp * gw;
+  if (grp >= ngrp) return;
+  const int npatch = (p_hi - p_lo) * g;
+  const unsigned smax_slot = (unsigned)(S - 1);
+  bf16_t* o = out + ((long)img * g * g + (long)p_lo * g) * ldo;
+  for (int piece = lp; piece < c8; piece += gw) {
+    const PiecePairs pp = piece_pairs(piece, C, P);
+    float inv[4], bias[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      inv[k] = sel4(tp.inv_std, pp.c[k]);
+      bias[k] = sel4(tp.nbias, pp.c[k]);
+    }
+    int pyl = grp / g, pxi = grp % g;  // patch row within the band, patch column
+    for (int pt = grp; pt < npatch; pt += ngrp) {
+      uint32_t w[4];
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        w[k] = 0u;  // pad columns
+        if (pp.c[k] >= 0) {
+          const Tap ry = rows[pyl * P + pp.ky[k]];
+          // slots of the two source rows (a zero-fill row reads slot 0 and drops it; the
+          // unsigned min keeps any index inside Hs)
+          const unsigned s0 = ry.ok ? min((unsigned)(ry.i0 - smin), smax_slot) : 0u;
+          const unsigned s1 = ry.ok ? min((unsigned)(ry.i1 - smin), smax_slot) : 0u;
+          const int xo = pxi * P + pp.kx[k];  // even: 8-B aligned in Hs
+          const float2 t = *reinterpret_cast<const float2*>(hs + (pp.c[k] * S + s0) * R + xo);
+          const float2 u = *reinterpret_cast<const float2*>(hs + (pp.c[k] * S + s1) * R + xo);
+          const float v0 = ry.ok ? lerp1(t.x, u.x, ry.l1) : 0.f;
+          const float v1 = ry.ok ? lerp1(t.y, u.y, ry.l1) : 0.f;
+          w[k] = pack2bf(__builtin_fmaf(v0, inv[k], bias[k]), __builtin_fmaf(v1, inv[k], bias[k]));
+        }
+      }
+      *reinterpret_cast<uint4*>(o + (long)pt * ldo + piece * 8) = uint4{w[0], w[1], w[2], w[3]};
+      pxi += ngrp;
+      while (pxi >= g) {
+        pxi -= g;
+        ++pyl;
+      }
+    }
+  }
+}
+
+// Large inputs: train_transform_kernel's per-pixel gathers, one 16-B piece of a padded patch row
+// per thread. fused != 0 normalises as x * (1/std) - mean/std (what the layout-0 LDS kernel does
+// for the same launch), else as (x - mean) / std (train_transform_kernel): the f32 image of
+// lc_train_transform's own routing through lc_patchify_pad stays bit-identical either way.
+__global__ void __launch_bounds__(256)
+train_transform_rows_kernel(int n, int C, int Hin, int Win, const float* __restrict__ x, int R,
+                            int pad, int crop_i, int crop_j, int flip, TfParams tp, int quantize,
+                            int fused, int P, int ldo, bf16_t* __restrict__ out) {
+  const int g = R / P, c8 = ldo >> 3;
+  const long total = (long)n * g * g * c8;
+  const float sh = (float)Hin / (float)R, sw = (float)Win / (float)R;
+  for (long e = blockIdx.x * (long)blockDim.x + threadIdx.x; e < total;
+       e += (long)gridDim.x * blockDim.x) {
+    const int piece = (int)(e % c8);
+    const long row = e / c8;
+    const int pxi = (int)(row % g);
+    const long r1 = row / g;
+    const int pyi = (int)(r1 % g), img = (int)(r1 / g);
+    const PiecePairs pp = piece_pairs(piece, C, P);
+    uint32_t w[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      w[k] = 0u;  // pad columns
+      const int c = pp.c[k];
+      if (c < 0) continue;
+      const float* src = x + ((long)img * C + c) * Hin * Win;
+      const int py = pyi * P + pp.ky[k] + crop_i - pad;  // row in the resized image
+      int y0 = 0, y1 = 0;
+      float ly = 0.f;
+      const bool row_in = py >= 0 && py < R;
+      if (row_in) lin_src(py, sh, Hin, y0, y1, ly);
+      float v[2];
+#pragma unroll
+      for (int j = 0; j < 2; ++j) {
+        const int xo = pxi * P + pp.kx[k] + j;
+        const int xs = flip ? (R - 1 - xo) : xo;  // hflip after the crop
+        const int px = xs + crop_j - pad;
+        float val = 0.f;                           // RandomCrop's zero fill
+        if (row_in && px >= 0 && px < R) {
+          int x0, x1;
+          float lx;
+          lin_src(px, sw, Win, x0, x1, lx);
+          const float a = quant(src[y0 * Win + x0], quantize), b = quant(src[y0 * Win + x1], quantize);
+          const float cc = quant(src[y1 * Win + x0], quantize), d = quant(src[y1 * Win + x1], quantize);
+          val = lerp1(lerp1(a, b, lx), lerp1(cc, d, lx), ly);
+        }
+        v[j] = fused ? __builtin_fmaf(val, sel4(tp.inv_std, c), sel4(tp.nbias, c))
+                     : (val - sel4(tp.mean, c)) / sel4(tp.std_, c);
+      }
+      w[k] = pack2bf(v[0], v[1]);
+    }
+    *reinterpret_cast<uint4*>(out + row * ldo + piece * 8) = uint4{w[0], w[1], w[2], w[3]};
+  }
+}
+
+}  // namespace
+
+extern "C" {
+
+int lc_train_transform_rows(hipStream_t st, int n, int C, int Hin, int Win, const float* x, int R,
+                            int pad, int crop_i, int crop_j, int flip, const float* mean_host,
+                            const float* std_host, int quantize, int patch, int ldo, void* out) {
+  LC_CHECK_ARG(n > 0 && C >= 1 && C <= 4 && Hin > 0 && Win > 0 && R > 0 && R % 4 == 0);
+  LC_CHECK_ARG(pad >= 0 && crop_i >= 0 && crop_j >= 0 && crop_i <= 2 * pad && crop_j <= 2 * pad);
+  LC_CHECK_ARG(mean_host != nullptr && std_host != nullptr && x != nullptr && out != nullptr);
+  LC_CHECK_ARG(patch > 0 && patch % 2 == 0 && R % patch == 0);
+  LC_CHECK_ARG((long)C * patch * patch <= (long)ldo && ldo % 8 == 0);
+  LC_CHECK_ARG((reinterpret_cast<uintptr_t>(out) & 15) == 0);
+  for (int c = 0; c < C; ++c) LC_CHECK_ARG(std_host[c] != 0.f);
+  if (patch == 16 && ldo == C * 256)  // the patch-16 kernels' own layout
+    return lc_train_transform(st, n, C, Hin, Win, x, R, pad, crop_i, crop_j, flip, mean_host,
+                              std_host, quantize, 1, 16, out);
+  TfParams tp{};
+  for (int c = 0; c < C; ++c) {
+    tp.mean[c] = mean_host[c];
+    tp.std_[c] = std_host[c];
+    tp.inv_std[c] = 1.0f / std_host[c];
+    tp.nbias[c] = -mean_host[c] / std_host[c];
+  }
+  bf16_t* o = static_cast<bf16_t*>(out);
+  const int g = R / patch;
+  // lc_train_transform's layout-0 routing: the LDS kernel (fused normalise) or the gather kernel
+  const size_t img_elems = ((size_t)C * Hin * Win + 3) & ~(size_t)3;
+  const bool fused = img_elems * sizeof(float) + 2 * (size_t)R * 16 <= 64 * 1024 && R / 4 <= 256;
+  if (fused) {
+    // the separable kernel: bands of patch rows per image, about four workgroups per CU when the
+    // grid allows; more bands (fewer source rows each) until a band's LDS fits 64 KB
+    int bands = (int)((4L * cu_count() + n - 1) / n);
+    bands = bands < 1 ? 1 : (bands > g ? g : bands);
+    for (; bands <= g; ++bands) {
+      const long ob = (long)((g + bands - 1) / bands) * patch;  // output rows of the largest band
+      // source rows ob consecutive output rows tap: their span, the second tap, rounding slack
+      long S = ((ob - 1) * Hin + R - 1) / R + 3;
+      S = S < Hin ? S : Hin;
+      const size_t sep_bytes =
+          ((((size_t)C * S * Win + 3) & ~(size_t)3) + (size_t)C * S * R) * sizeof(float) +
+          (size_t)(ob + R) * sizeof(Tap);
+      if (sep_bytes > 64 * 1024) continue;
+      hipLaunchKernelGGL(train_transform_rows_sep_kernel, dim3(n, bands), dim3(256), sep_bytes, st,
+                         C, Hin, Win, x, R, pad, crop_i, crop_j, flip, tp, quantize, patch, ldo,
+                         (int)S, (int)ob, o);
+      LC_LAUNCH_RET();
+    }
+  }
+  const long total = (long)n * g * g * (ldo / 8);
+  long blocks = (total + 255) / 256;
+  if (blocks > 8192) blocks = 8192;
+  hipLaunchKernelGGL(train_transform_rows_kernel, dim3((unsigned)blocks), dim3(256), 0, st, n, C,
+                     Hin, Win, x, R, pad, crop_i, crop_j, flip, tp, quantize, (int)fused, patch,
+                     ldo, o);
+  LC_LAUNCH_RET();
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------------
 // AutoAugment ops on the uint8 batch (the 'autoaug' branch of methods/_trainer.py:215-229:
 // (x*255).type(uint8) -> transforms.AutoAugment(policy) -> .float()/255). torchvision draws one
 // sub-policy per call for the whole batch tensor; the host (lcclip/transforms.py) draws it and

@@ -41,6 +41,7 @@ from . import ops
 from .ops import BF16, F16, F32, EPI_BF16, EPI_F32, EPI_GELU, EPI_GELU_D, EPI_MUL, EPI_RESID
 from .ops import EPI_RESID16
 from .ops import EPI_GELU_D_Q8, EPI_MUL_Q8
+from .transforms import patch_row_width
 
 _seed_counter = itertools.count(1)
 
@@ -1171,7 +1172,7 @@ class ImageTower:
             K = v.conv1.weight[0].numel()
             # conv1's GEMM takes K % 64 == 0: a patch size that gives another K (14: 588) runs
             # at Kp = 640 on zero pad columns, which add exact zeros to every sum
-            self.conv_k = Kp = -(-K // 64) * 64
+            self.conv_k = Kp = patch_row_width(v.conv1.weight.shape[-1], v.conv1.weight.shape[1])
             if Kp == K:
                 self.conv_w = _empty((W, K), dt, dev)
                 ops.merge_weight(v.conv1.weight.detach().reshape(W, -1), None, None, 0.0, self.conv_w)
@@ -1208,12 +1209,13 @@ class ImageTower:
         Kp = self.conv_k
         if img.dim() == 2:
             # conv1's bf16 im2col rows, already produced by the fused train transform
-            # (lcclip.transforms.TrainTransform(..., layout="patches"))
-            if Kp != 3 * P * P:
-                raise ValueError(f"patch-row input needs 3 * patch^2 % 64 == 0 (patch {P}): pass "
-                                 "NCHW images")
-            if img.dtype != BF16 or img.shape[1] != 3 * P * P or img.shape[0] % npch:
-                raise ValueError(f"patch input must be bf16 [n*{npch}, {3 * P * P}]")
+            # (lcclip.transforms.TrainTransform(..., layout="patches")), at conv1's GEMM width:
+            # a padded-K model (patch 14: 640) takes rows whose pad columns are zero, which is
+            # trusted as conv_w's zero pad columns are
+            if img.dtype != BF16 or img.shape[1] != Kp or img.shape[0] % npch:
+                pad = "" if Kp == 3 * P * P else f" ({3 * P * P} data columns, then zeros)"
+                raise ValueError(f"patch input must be bf16 [n*{npch}, {Kp}]{pad}: conv1's patch "
+                                 f"rows of a patch-{P} model (transforms.patch_row_width)")
             n = img.shape[0] // npch
             # (the fp16 tower: bf16 -> half is exact for normalised pixels, |x| < 2^15)
             patches = img.contiguous().to(self.stack.dt)

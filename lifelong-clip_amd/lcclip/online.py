@@ -18,7 +18,7 @@ Reference loop (methods/_trainer.py:320-357, methods/adapter_clip.py:34-176):
 online_train (adapter_clip.py:49-107): remap y into the batch's class list, GPU train
 transform, tokens of the class list, fwd + CE-on-probs + bwd + AdamW (OnlineTrainer.step).
 
-Pieces: SiBlurryStream / ClassBook (stream.py), TrainTransform (transforms.py), OnlineTrainer
+Pieces: SiBlurryStream / ClassBook (stream.py), TrainTransform / EvalTransform (transforms.py), OnlineTrainer
 (trainer.py), online_evaluate / AUCTracker / summarize (evaluate.py). The scheduler is the
 reference's 'default' (constant LambdaLR, utils/train_utils.py:57-58), i.e. no-op. The replay
 memory is disabled on this path (memory_batchsize = 0). A_auc: the reference
@@ -36,13 +36,18 @@ from .evaluate import AUCTracker, online_evaluate, summarize
 
 class OnlineLoop:
     """trainer: OnlineTrainer over an AdapterCLIP wrapper; stream: SiBlurryStream over the
-    training targets; book: ClassBook(class_names); train_x / test_x: f32 [n, 3, H, W] in [0, 1]
-    (ToTensor values) when a transform is given, else already-normalised model inputs;
-    tokenize(names) -> int64 [C, 77] token ids; transform: TrainTransform or None."""
+    training targets; book: ClassBook(class_names); tokenize(names) -> int64 [C, 77] token ids.
+    train_x: f32 [n, 3, H, W] in [0, 1] (ToTensor values) when `transform` (a TrainTransform) is
+    given, which every training batch then goes through with layout="patches"; else
+    already-normalised model inputs. test_x: the same ToTensor values when `eval_transform` (an
+    EvalTransform: the reference's test_transform, _trainer.py:243-247) is given, which every
+    test batch then goes through with layout="patches" on the device; else already-normalised
+    model inputs, handed to the wrapper as they are. The two are independent: `transform` never
+    touches test_x."""
 
     def __init__(self, trainer, stream, book, train_x, train_y, test_x, test_y, tokenize,
                  transform=None, batch_size=16, online_iter=3, epochs=1, eval_period=None,
-                 test_batch=256, n_buckets=10, on_step=None):
+                 test_batch=256, n_buckets=10, on_step=None, eval_transform=None):
         self.trainer = trainer
         self.wrapper = trainer.wrapper
         self.stream = stream
@@ -51,6 +56,7 @@ class OnlineLoop:
         self.test_x, self.test_y = test_x, torch.as_tensor(test_y).long()
         self.tokenize = tokenize
         self.transform = transform
+        self.eval_transform = eval_transform
         self.batch_size = int(batch_size)
         self.online_iter = int(online_iter)
         self.epochs = int(epochs)
@@ -99,7 +105,10 @@ class OnlineLoop:
         idx = keep.nonzero().flatten()                           # OnlineTestSampler
         for s in range(0, len(idx), self.test_batch):
             b = idx[s:s + self.test_batch]
-            yield self.test_x[b], self.test_y[b]
+            x = self.test_x[b]
+            if self.eval_transform is not None:                  # _trainer.py:243-247
+                x = self.eval_transform(x.to(self.device), layout="patches")
+            yield x, self.test_y[b]
 
     def evaluate(self, n_classes):
         """online_evaluate with the tokens of class_names[:n_classes] (online_after_task)."""

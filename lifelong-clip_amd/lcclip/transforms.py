@@ -19,7 +19,11 @@ uint8-quantised batch (one workgroup per image, the image in LDS), and lc_train_
 the bilinear resize, the padded crop, the flip and the normalisation in a single pass over the
 output (or, with no augmentation op active, the uint8 round trip itself). layout="patches" writes
 conv1's bf16 im2col rows directly ([n*196, 768] for ViT-B/16), which ImageTower.forward accepts in
-place of an image batch, so the f32 224x224 batch never touches HBM.
+place of an image batch, so the f32 224x224 batch never touches HBM. A patch size whose 3 P^2 is
+no multiple of 64 (ViT-L/14: 588) gets its rows at conv1's padded width ([n*256, 640], pad
+columns zero) from lc_train_transform_rows, bit-identical to the f32 batch through
+lc_patchify_pad. EvalTransform is the reference's test_transform (Resize + Normalize) through the
+same launches, for the loop's evaluation batches.
 
 The AutoAugment policy tables, magnitude bins and op semantics restate torchvision 0.16.2
 (requirements.yaml:269; transforms/autoaugment.py, transforms/_functional_tensor.py), which is not
@@ -286,12 +290,113 @@ def autoaugment(x, ops):
     return out
 
 
+def patch_row_width(patch, channels=3):
+    """Columns of one of conv1's im2col rows as its GEMM takes them: C * P^2 rounded up to a
+    multiple of 64 (768 for patch 16, 3072 for 32; 640 for 14, whose 588 data columns are
+    followed by zero pad columns). ImageTower sizes conv1's staged weight by the same rule."""
+    return -(-int(channels) * int(patch) ** 2 // 64) * 64
+
+
+def train_transform_rows(x, out, mean, std, inp_size, patch, padding=0, crop=(0, 0), flip=False,
+                         quantize=False):
+    """lc_train_transform_rows: resize + padded crop + flip + normalise of the f32 [n, C, H, W]
+    batch x straight into conv1's bf16 patch rows out [n * (inp_size / patch)^2, ldo] for any even
+    patch size and any ldo >= C * patch^2 (ldo % 8 == 0); the columns past C * patch^2 are
+    written as zero. Returns out."""
+    n, C, H, W = x.shape
+    R, P = int(inp_size), int(patch)
+    if P <= 0 or R % P:
+        raise ValueError("inp_size must be a multiple of the patch size")
+    if (out.dim() != 2 or out.dtype != torch.bfloat16 or not out.is_contiguous()
+            or out.device != x.device or out.shape[0] != n * (R // P) ** 2):
+        raise ValueError(f"out must be a contiguous bf16 [{n * (R // P) ** 2}, ldo] buffer on "
+                         "the batch's device")
+    m = (ctypes.c_float * C)(*mean)
+    s = (ctypes.c_float * C)(*std)
+    call("lc_train_transform_rows", stream_of(x), n, C, H, W, ptr(x), R, int(padding),
+         int(crop[0]), int(crop[1]), int(bool(flip)), ctypes.cast(m, ctypes.c_void_p),
+         ctypes.cast(s, ctypes.c_void_p), int(bool(quantize)), P, out.shape[1], ptr(out))
+    return out
+
+
+def _resize_crop_normalize(x, mean, std, R, P, padding, i, j, flip, quantize, layout, out):
+    """The transform launch shared by TrainTransform and EvalTransform. layout "nchw": f32
+    [n, C, R, R]. layout "patches": conv1's bf16 rows, [n*g*g, C*P*P] from lc_train_transform
+    when C*P*P is a multiple of 64 (patch 16 / 32), else [n*g*g, patch_row_width(P, C)] from
+    lc_train_transform_rows (patch 14); an `out` buffer of another width selects the latter too."""
+    n, C, H, W = x.shape
+    if layout == "nchw":
+        if out is None:
+            out = torch.empty(n, C, R, R, dtype=torch.float32, device=x.device)
+        elif (out.shape != (n, C, R, R) or out.dtype != torch.float32 or not out.is_contiguous()
+              or out.device != x.device):
+            raise ValueError(f"out must be a contiguous f32 [{n}, {C}, {R}, {R}] buffer")
+        lay = 0
+    elif layout == "patches":
+        if R % P:
+            raise ValueError("inp_size must be a multiple of the patch size")
+        g = R // P
+        K = C * P * P
+        if out is None:
+            out = torch.empty(n * g * g, patch_row_width(P, C), dtype=torch.bfloat16,
+                              device=x.device)
+        if K % 64 or out.dim() != 2 or out.shape[1] != K:
+            return train_transform_rows(x, out, mean, std, R, P, padding, (i, j), flip, quantize)
+        if (out.shape[0] != n * g * g or out.dtype != torch.bfloat16 or not out.is_contiguous()
+                or out.device != x.device):
+            raise ValueError(f"out must be a contiguous bf16 [{n * g * g}, {K}] buffer")
+        lay = 1
+    else:
+        raise ValueError("layout must be 'nchw' or 'patches'")
+    m = (ctypes.c_float * C)(*mean)
+    s = (ctypes.c_float * C)(*std)
+    call("lc_train_transform", stream_of(x), n, C, H, W, ptr(x), R, int(padding), int(i), int(j),
+         int(bool(flip)), ctypes.cast(m, ctypes.c_void_p), ctypes.cast(s, ctypes.c_void_p),
+         int(quantize), lay, P, ptr(out))
+    return out
+
+
+class EvalTransform:
+    """`self.test_transform` of methods/_trainer.py:243-247 on the GPU: Resize((S, S)) +
+    Normalize(mean, std) of a ToTensor batch, f32 [n, C, H, W] in [0, 1]. It is the train
+    transform's launch with no padding, no crop offset, no flip, no uint8 round trip and no
+    draw from any generator; layouts as TrainTransform ("nchw", "patches").
+
+    Known deviation (parity unpinned against PIL): the reference resizes the PIL image, whose
+    result is 8-bit, before ToTensor; this resizes the f32 ToTensor values with the train
+    transform's bilinear arithmetic (align_corners = False, no antialias), so the two differ
+    by the resampler and by the 8-bit rounding of the resized image."""
+
+    def __init__(self, mean, std, inp_size=224, patch=16):
+        if len(mean) != len(std) or not 1 <= len(mean) <= 4:
+            raise ValueError("mean/std must have one entry per channel (1..4)")
+        self.mean = [float(m) for m in mean]
+        self.std = [float(s) for s in std]
+        self.inp_size = int(inp_size)
+        self.patch = int(patch)
+
+    @classmethod
+    def for_dataset(cls, name, **kw):
+        mean, std = DATASET_STATS[name]
+        return cls(mean, std, **kw)
+
+    def __call__(self, x, layout="nchw", out=None):
+        if x.dim() != 4 or x.dtype != torch.float32:
+            raise ValueError("EvalTransform expects an f32 [n, C, H, W] batch")
+        if x.shape[1] != len(self.mean):
+            raise ValueError(f"batch has {x.shape[1]} channels, mean/std have {len(self.mean)}")
+        return _resize_crop_normalize(x.contiguous(), self.mean, self.std, self.inp_size,
+                                      self.patch, 0, 0, 0, False, 0, layout, out)
+
+
 class TrainTransform:
     """`self.train_transform` of methods/_trainer.py:236-242 on the GPU.
 
     x: f32 [n, C, H, W] on the GPU with ToTensor values in [0, 1] (the dataset's transform,
     _trainer.py:197). Returns the normalised [n, C, S, S] f32 batch, or with
-    layout="patches" the bf16 patch rows of conv1 (see module docstring)."""
+    layout="patches" the bf16 patch rows of conv1 (see module docstring). out: optional
+    result buffer (for "patches" with a width other than C * patch^2, e.g. a padded row
+    stride, the rows go through lc_train_transform_rows)."""
 
     def __init__(self, mean, std, inp_size=224, padding=4, autoaug=True, patch=16,
                  generator=None, policy=None):
@@ -325,7 +430,7 @@ class TrainTransform:
         flip = bool(torch.rand(1, generator=self.generator) < 0.5)
         return ops, i, j, flip
 
-    def __call__(self, x, params=None, layout="nchw"):
+    def __call__(self, x, params=None, layout="nchw", out=None):
         if params is None:
             params = self.draw(x.shape[-2], x.shape[-1])
         if len(params) == 3:  # (crop_i, crop_j, flip): no augmentation op
@@ -333,9 +438,8 @@ class TrainTransform:
         ops, i, j, flip = params
         if x.dim() != 4 or x.dtype != torch.float32:
             raise ValueError("TrainTransform expects an f32 [n, C, H, W] batch")
-        n, C, H, W = x.shape
-        if C != len(self.mean):
-            raise ValueError(f"batch has {C} channels, mean/std have {len(self.mean)}")
+        if x.shape[1] != len(self.mean):
+            raise ValueError(f"batch has {x.shape[1]} channels, mean/std have {len(self.mean)}")
         x = x.contiguous()
         quantize = int(self.autoaug)
         if ops:
@@ -343,21 +447,6 @@ class TrainTransform:
                 raise ValueError("AutoAugment ops need the autoaug branch")
             x = autoaugment(x, ops)  # uint8 round trip + ops, written back as k / 255
             quantize = 0
-        R, P = self.inp_size, self.patch
-        if layout == "nchw":
-            out = torch.empty(n, C, R, R, dtype=torch.float32, device=x.device)
-            lay = 0
-        elif layout == "patches":
-            if R % P:
-                raise ValueError("inp_size must be a multiple of the patch size")
-            g = R // P
-            out = torch.empty(n * g * g, C * P * P, dtype=torch.bfloat16, device=x.device)
-            lay = 1
-        else:
-            raise ValueError("layout must be 'nchw' or 'patches'")
-        mean = (ctypes.c_float * C)(*self.mean)
-        std = (ctypes.c_float * C)(*self.std)
-        call("lc_train_transform", stream_of(x), n, C, H, W, ptr(x), R, self.padding, int(i),
-             int(j), int(bool(flip)), ctypes.cast(mean, ctypes.c_void_p),
-             ctypes.cast(std, ctypes.c_void_p), quantize, lay, P, ptr(out))
-        return out
+        return _resize_crop_normalize(x, self.mean, self.std, self.inp_size, self.patch,
+                                      self.padding, int(i), int(j), bool(flip), quantize, layout,
+                                      out)
